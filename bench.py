@@ -6,8 +6,15 @@ GPU (half corpus points + 0.1*N(0,I), half fresh N(0,I); seed 1 + rank), k = 10.
 A step = one libcwq cwq_score_topk call over the batch (scan + path score + top-k
 + merge + sentence ids), inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset c1|c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset c1|c2|c3|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it builds the tree and the
+index, warms up, times the K steps and prints one JSON line (`value` = queries/s,
+`ms_per_step` = milliseconds per timed step).  `--dump-outputs DIR` then writes what the
+last timed step returned -- the arrays a cwq_score_topk caller receives -- as DIR/ids.npy
+(float64) and DIR/scores.npy (float32); the inputs are seeded, so two builds can be
+compared output for output.  The other legs, described below, run only with `--full`.
 
 Multi-GPU (the functions of rag-cobweb_amd/dist.py, covered by tests/test_dist.py on
 gloo): rank 0 synthesises the tree and `broadcast_tree` sends the frozen node
@@ -17,7 +24,9 @@ over ranks.  Preset c3 (default): every rank scans its own 10k-query batch (weak
 scaling).  Preset c4 (BASELINE configs[3]): 10M x 1024, 100k queries per step split
 over the ranks by `sharded_query` (strong scaling).  No collective in the timed loop.
 
-Also reported: `per_call` (the reference harness's one-query-per-call mode at nq = 1, 8,
+With `--full`, also reported: `roofline` (HIP-event time of the dominant kernel, in calls of
+its own), `recall@10` against exact brute force, `per_call` (the reference harness's
+one-query-per-call mode at nq = 1, 8,
 64, plus the wrapper's numpy-query Fast and Basic calls: harness_call_nq1,
 harness_basic_nq1), `hier` (a device-ifit Cobweb tree over a 100k x 768 clustered corpus:
 ifit inserts/s, Fast batch / per call, Basic batch / per call, the filter and pruning
@@ -158,6 +167,26 @@ PRESETS = {
     "c2": dict(n=100_000, dim=768, queries=1_000, strong=False),
     "c5": dict(n=8_800_000, dim=256, queries=10_000, strong=False),
 }
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, ids, scores, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the (ids, scores) of the last timed step as DIR/ids.npy (float64: sentence
+    ids, exact) and DIR/scores.npy (float32).  A result over `limit` bytes is cut to a fixed
+    seeded sample of its query rows (their numbers in DIR/rows.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    ids = ids.cpu().numpy().astype(np.float64)
+    scores = scores.cpu().numpy().astype(np.float32)
+    row_bytes = (ids.nbytes + scores.nbytes + 8 * len(ids)) / max(1, len(ids))
+    limit -= 3 * 4096                                      # room for the .npy headers
+    if len(ids) * row_bytes > limit:
+        rows = np.sort(np.random.default_rng(0).choice(len(ids), int(limit // row_bytes), replace=False))
+        ids, scores = ids[rows], scores[rows]
+        np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "ids.npy"), ids)
+    np.save(os.path.join(dirname, "scores.npy"), scores)
 
 
 def per_call(index, Q, k, nqs=(1, 8, 64), reps=20):
@@ -371,6 +400,62 @@ def hier_leg(pkg, n=100_000, dim=768, n_clusters=100, nq=1000, k=10, calls=100):
     return out
 
 
+def roofline_leg(index, Ql, k, st, N, D, pmc_file):
+    """--full: the dominant kernel's time (HIP events on the launch stream, three calls of their
+    own with timing on) against its pipe's peak, with the HBM traffic and the held clock of a
+    matching PMC summary.  `st` = last_stats() of a timed step."""
+    index.set_timing(True)
+    tms = []
+    for _ in range(3):
+        index.score_topk(Ql, k)
+        tms.append(index.last_timing())
+    index.set_timing(False)
+    call_ms = float(np.mean([t["call_ms"] for t in tms]))
+    nql = len(Ql)
+    NL = index.info["leaf_rows"]
+    if st["filter_used"]:
+        # bf16-MFMA candidate filter (cwq_mfma.hip fgemm): 2*D flops per (query, leaf row)
+        kern_ms = float(np.mean([t["fgemm_ms"] for t in tms]))
+        flops_launch = 2.0 * D * NL * nql
+        peak, kname, pipe = PEAK_BF16_TFLOPS, "fgemm_kernel<0> (bf16 MFMA filter pass)", "bf16 MFMA dense"
+        launches = max(1, round(float(np.mean([t["leaf_scan_launches"] for t in tms]))))   # filter phases
+        phases = {"sample_ms": round(float(np.mean([t["sample_ms"] for t in tms])), 3),
+                  "fgemm_ms": round(kern_ms, 3),
+                  "rerank_ms": round(float(np.mean([t["rerank_ms"] for t in tms])), 3)}
+    else:
+        kern_ms = float(np.mean([t["leaf_scan_ms"] / max(1, t["leaf_scan_launches"]) for t in tms]))
+        flops_launch = 4.0 * D * NL * nql                 # SURVEY §8(d): 4*Nn*D per query (leaf rows)
+        peak, kname, pipe = PEAK_FP32_TFLOPS, "scan_kernel<ISO,TOPK> (exact fp32 leaf scan)", "fp32 VALU"
+        phases = {}
+        launches = 1
+    achieved_tf = flops_launch / (kern_ms * 1e-3) / 1e12
+    traffic = clk = pmc_used = None
+    for pf in pmc_candidates(pmc_file):
+        try:
+            pm = json.load(open(pf))
+        except (OSError, ValueError):
+            continue
+        if pm.get("workload") == [N, D, nql, k] and pm.get("kernel") == kname.split(" ")[0]:
+            # per step (the filter launches of one call), like `achieved`; files before round 5
+            # stored the per-call figure under the key hbm_bytes_per_launch
+            traffic = pm.get("hbm_bytes_per_call", pm.get("hbm_bytes_per_launch"))
+            clk = pm.get("effective_clock_ghz")   # GRBM_GUI_ACTIVE / kernel time, same PMC run
+            pmc_used = os.path.relpath(pf, ROOT)
+            break
+    return {"bound": "mfma", "pipe": pipe,
+            "achieved": round(achieved_tf, 2), "peak": peak, "unit": "TFLOP/s",
+            "frac": round(achieved_tf / peak, 4), "traffic": traffic, "traffic_unit": "bytes per step",
+            "pmc_file": pmc_used,
+            "kernel": kname, "kernel_ms": round(kern_ms, 3), "launches_per_step": launches,
+            "avg_launch_ms": round(kern_ms / launches, 3),
+            "call_ms": round(call_ms, 3), "flops_per_step": flops_launch, "phases_ms": phases,
+            # the dense peak assumes the 2.4 GHz peak clock; under this load the chip
+            # holds the PMC-measured clock, so this is the fraction of what it can issue
+            "clock_ghz_held": clk,
+            "frac_at_held_clock": (round(achieved_tf / (peak * clk / PEAK_CLOCK_GHZ), 4)
+                                   if clk and pipe.startswith("bf16") else None)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -383,6 +468,11 @@ def main():
                     help="queries per GPU per step (weak) or per step in total (--strong)")
     ap.add_argument("--strong", action="store_true", default=None, help="split --queries over the ranks")
     ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the (ids, scores) the last timed step returned to DIR/ids.npy, DIR/scores.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, recall@10, per-call, hierarchical and CPU-baseline legs "
+                         "(the options below choose among them)")
     ap.add_argument("--cpu-sample", type=int, default=20, help="CPU baseline queries at all host threads")
     ap.add_argument("--cpu-sample-1t", type=int, default=20, help="CPU baseline queries at 1 thread")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -397,6 +487,8 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="rehearsal only: gloo lets several ranks share one GPU (RCCL refuses that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     pre = PRESETS[args.preset]
     N = args.n or pre["n"]
     D = args.dim or pre["dim"]
@@ -478,58 +570,28 @@ def main():
     # (the index holds its own), so a rank holds the index + its workspace only
     Ql = Q[q_lo:q_hi]
     nql = q_hi - q_lo
-    n_rec = min(args.recall_queries, nql)
+    n_rec = min(args.recall_queries, nql) if args.full else 0
     gt = recall_truth(pkg, X, Ql, k, n_rec) if rank == 0 and n_rec > 0 else None
-    Xh = X.cpu().numpy() if rank == 0 and world == 1 and not args.no_cpu_baseline else None
+    Xh = X.cpu().numpy() if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline else None
     del X, mean
     torch.cuda.empty_cache()
     used_freed = dev_used()
 
     # ---- timed loop (barrier + sync on both sides, max over ranks) ----
-    dt = D_.timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize)
-    qps = total_q * args.steps / dt
-    ids, scores = step()
+    last = [None]
 
-    # ---- dominant kernel timing (HIP events on the launch stream) ----
+    def kept_step():                      # the timed path, its latest result kept for --dump-outputs
+        last[0] = step()
+
+    dt = D_.timed_steps(kept_step, args.steps, args.warmup, torch.cuda.synchronize)
+    qps = total_q * args.steps / dt
+    ids, scores = last[0]
     st = index.last_stats()
-    index.set_timing(True)
-    tms = []
-    for _ in range(3):
-        index.score_topk(Ql, k)
-        tms.append(index.last_timing())
-    index.set_timing(False)
-    call_ms = float(np.mean([t["call_ms"] for t in tms]))
-    NL = index.info["leaf_rows"]
-    if st["filter_used"]:
-        # bf16-MFMA candidate filter (cwq_mfma.hip fgemm): 2*D flops per (query, leaf row)
-        kern_ms = float(np.mean([t["fgemm_ms"] for t in tms]))
-        flops_launch = 2.0 * D * NL * nql
-        peak, kname, pipe = PEAK_BF16_TFLOPS, "fgemm_kernel<0> (bf16 MFMA filter pass)", "bf16 MFMA dense"
-        launches = max(1, round(float(np.mean([t["leaf_scan_launches"] for t in tms]))))   # filter phases
-        phases = {"sample_ms": round(float(np.mean([t["sample_ms"] for t in tms])), 3),
-                  "fgemm_ms": round(kern_ms, 3),
-                  "rerank_ms": round(float(np.mean([t["rerank_ms"] for t in tms])), 3)}
-    else:
-        kern_ms = float(np.mean([t["leaf_scan_ms"] / max(1, t["leaf_scan_launches"]) for t in tms]))
-        flops_launch = 4.0 * D * NL * nql                 # 4*Nn*D per query (leaf rows)
-        peak, kname, pipe = PEAK_FP32_TFLOPS, "scan_kernel<ISO,TOPK> (exact fp32 leaf scan)", "fp32 VALU"
-        phases = {}
-        launches = 1
-    achieved_tf = flops_launch / (kern_ms * 1e-3) / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ids, scores)
+
+    roof = roofline_leg(index, Ql, k, st, N, D, args.pmc_file) if args.full else None
     bytes_q = 8.0 * (N + 1) * D + 8.0 * 2 * N + 4.0 * D + 12.0 * k   # SURVEY §8(d) bytes per query
-    traffic = clk = pmc_used = None
-    for pf in pmc_candidates(args.pmc_file):
-        try:
-            pm = json.load(open(pf))
-        except (OSError, ValueError):
-            continue
-        if pm.get("workload") == [N, D, nql, k] and pm.get("kernel") == kname.split(" ")[0]:
-            # per step (the filter launches of one call), like `achieved`; files before round 5
-            # stored the per-call figure under the key hbm_bytes_per_launch
-            traffic = pm.get("hbm_bytes_per_call", pm.get("hbm_bytes_per_launch"))
-            clk = pm.get("effective_clock_ghz")   # GRBM_GUI_ACTIVE / kernel time, same PMC run
-            pmc_used = os.path.relpath(pf, ROOT)
-            break
 
     torch.cuda.empty_cache()
     used_steady = dev_used()              # + the handle's workspace after the timed calls
@@ -540,8 +602,8 @@ def main():
            "device_total": torch.cuda.mem_get_info(dev)[1],
            "note": "device-wide used bytes (mem_get_info) on this rank, sampled after index create (caller's "
                    "mean still resident; the per-call int8 panel is built with the index), after the caller's "
-                   "copies are freed, after the timed steps (index + the handle's workspace) and after the per-call "
-                   "legs"}
+                   "copies are freed, after the timed steps (index + the handle's workspace) and, with "
+                   "--full, after the per-call legs"}
 
     rec_l2 = rec_ip = rec_tgt = None
     if gt is not None:
@@ -549,7 +611,7 @@ def main():
         rec_l2, rec_ip, rec_tgt = recall_at_k(gt, ids, tg, k, n_rec)
 
     pc = None
-    if rank == 0 and not args.no_per_call:
+    if args.full and rank == 0 and not args.no_per_call:
         pc = per_call(index, Ql, k)
         pc["harness_call_nq1"] = per_call_harness(pkg, index, Ql, k)
         try:
@@ -564,7 +626,7 @@ def main():
         mem["peak_sampled"] = max(mem["peak_sampled"], mem["device_used_after_per_call"])
 
     hier = None
-    if rank == 0 and world == 1 and not args.no_hier:
+    if args.full and rank == 0 and world == 1 and not args.no_hier:
         log(f"hierarchical leg: device ifit of {args.hier_n} x 768 clustered rows + queries ...")
         try:
             hier = hier_leg(pkg, n=args.hier_n)
@@ -585,6 +647,7 @@ def main():
             "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1000 * dt / args.steps, 3), "higher_is_better": True,
             "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "full": args.full,
             "config": {"workload": f"Cobweb Fast top-{k}: synthetic flat-synth tree (root + {N} leaves), "
                                    f"X~N(0,I) {N}x{D} fp32, " +
                                    (f"{Qarg} queries/step split over {world} GPU(s)" if strong else
@@ -593,18 +656,7 @@ def main():
                        "queries_per_gpu": nql, "k": k, "tree": "flat-synth",
                        "parallelism": f"query-shard x{world}, index broadcast over " + ("RCCL" if args.dist_backend == "nccl" else "gloo (rehearsal)") if world > 1
                        else "single GPU"},
-            "roofline": {"bound": "mfma", "pipe": pipe,
-                         "achieved": round(achieved_tf, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved_tf / peak, 4), "traffic": traffic, "traffic_unit": "bytes per step",
-                         "pmc_file": pmc_used,
-                         "kernel": kname, "kernel_ms": round(kern_ms, 3), "launches_per_step": launches,
-                         "avg_launch_ms": round(kern_ms / launches, 3),
-                         "call_ms": round(call_ms, 3), "flops_per_step": flops_launch, "phases_ms": phases,
-                         # the dense peak assumes the 2.4 GHz peak clock; under this load the chip
-                         # holds the PMC-measured clock, so this is the fraction of what it can issue
-                         "clock_ghz_held": clk,
-                         "frac_at_held_clock": (round(achieved_tf / (peak * clk / PEAK_CLOCK_GHZ), 4)
-                                                if clk and pipe.startswith("bf16") else None)},
+            "roofline": roof,
             "filter": {k_: st[k_] for k_ in ("filter_used", "fallback_queries", "candidates", "exact_reranks",
                                               "sample_rows")},
             # the reference algorithm reads every node's mean+var once per query; a batch
