@@ -151,6 +151,21 @@ int cwq_score_topk(cwq_index* idx, const float* q, int64_t nq, int32_t k, int64_
 int cwq_rank_scores(cwq_index* idx, const float* q, int64_t nq, float* out, void* stream);
 
 /*
+ * Backward of cwq_rank_scores: the reference documents cobweb_rank_scores as
+ * "Differentiable: return raw scores for all leaves" (CobwebWrapper.py:267-294), and its
+ * query-encoder training backpropagates a cross-entropy loss through the scores into the
+ * query embedding (src/training/cobweb_query_train.py:104-126).
+ *   grad_out: device [nq*n_sent] fp32, the upstream gradient of every score.  Entries of
+ *             sentences that are not in the tree (score -inf) are never read.
+ *   grad_q:   device [nq*dim] fp32, d(sum grad_out * scores)/dq.
+ * Needs no state of the forward call.  fp32 means throughout; no float atomics: the result
+ * is identical from run to run and a query's gradient does not depend on the batch it is
+ * in.  CWQ_ERR_ARG on a NULL argument (before any device work); nq == 0 is a no-op.
+ */
+int cwq_rank_scores_backward(cwq_index* idx, const float* q, int64_t nq, const float* grad_out, float* grad_q,
+                             void* stream);
+
+/*
  * Per-node Gaussian log-likelihood for every node in BFS order.
  *   full = 0: lp'(n) as CobwebWrapper.py:232-236 (no 2*pi term)
  *   full = 1: CobwebTorchNode.log_prob (CobwebTorchNode.py:100-104, with 2*pi)

@@ -2851,6 +2851,115 @@ extern "C" int cwq_rank_scores(cwq_index* ix, const float* q, int64_t nq, float*
   return CWQ_OK;
 }
 
+// Backward of cwq_rank_scores (cwq_grad.hip): the coefficient pass, the streaming reduction
+// over the three row classes, the slab sum.  Needs q, grad_out and the index only.
+extern "C" int cwq_rank_scores_backward(cwq_index* ix, const float* q, int64_t nq, const float* grad_out,
+                                        float* grad_q, void* stream) {
+  if (!ix || !q || !grad_out || !grad_q) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
+  if (nq == 0) return CWQ_OK;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DevGuard dg(ix->device);
+  hipStream_t s = (hipStream_t)stream;
+  WsUse wu(ix, s);
+  if (wu.rc) return wu.rc;
+  const int NL = ix->NL, NI = ix->NI, DP = ix->DP;
+  // slabs: a function of the index alone (a query's gradient is the same in any batch)
+  const int rps = grad_rows_per_slab((int64_t)ix->NL_iso + 2 * ((int64_t)ix->NL_an + NI), ix->cus);
+  const int ns_iso = (ix->NL_iso + rps - 1) / rps, ns_an = (ix->NL_an + rps - 1) / rps, ns_int = (NI + rps - 1) / rps;
+  const int nslab = ns_iso + ns_an + ns_int;
+  const int nsplit = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)ix->max_fanout + 4095) / 4096));
+  const int P = ix->max_fanout > 64 ? 16 : 1;
+  std::vector<int> lv;
+  for (auto& l : ix->levels) {
+    lv.push_back(l.first);
+    lv.push_back(l.second);
+  }
+  const size_t per_q = ((size_t)2 * std::max(NL, 1) + (size_t)(2 + nsplit) * std::max(NI, 1) + (size_t)nslab * DP) * 4;
+  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, per_q, false), 4096);
+  int rc;
+  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
+    const int nqc = (int)std::min(cq, nq - q0);
+    const int qtiles = (nqc + kXQ - 1) / kXQ;
+    const size_t nq16 = (size_t)qtiles * kXQ;
+    if ((rc = ix->reserve(nq16 * per_q + 8 * 256))) return rc;
+    Bump b(ix->ws, ix->ws_size);
+    GradCoefArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.G = grad_out + q0 * ix->n_sent;
+    ca.n_sent = ix->n_sent;
+    ca.nq = nqc;
+    ca.qtiles = qtiles;
+    ca.NL = NL;
+    ca.NL_iso = ix->NL_iso;
+    ca.NI = NI;
+    ca.sent_ptr = ix->sent_ptr;
+    ca.sent_ids = ix->sent_ids;
+    ca.meta = ix->row_meta;
+    ca.leaf_a0 = ix->int_leaf_a0;
+    ca.leaf_a1 = ix->int_leaf_a1;
+    ca.leaf_b0 = ix->int_leaf_b0;
+    ca.leaf_b1 = ix->int_leaf_b1;
+    ca.child_begin = ix->int_child_begin;
+    ca.child_end = ix->int_child_end;
+    ca.w_int = ix->w_int;
+    ca.lv = lv.data();
+    ca.nlev = (int)ix->levels.size();
+    ca.P = P;
+    ca.nsplit = nsplit;
+    ca.coefL = b.take<float>(nq16 * std::max(NL, 1));
+    ca.hL = b.take<float>(nq16 * std::max(NL, 1));
+    ca.cz = b.take<float>(nq16 * std::max(NI, 1) * nsplit);
+    ca.cI = b.take<float>(nq16 * std::max(NI, 1));
+    ca.coefI = b.take<float>(nq16 * std::max(NI, 1));
+    float* part = b.take<float>(nq16 * (size_t)nslab * DP);
+    HIPCHK(launch_grad_coef(ca, s));
+    GradStreamArgs g;
+    memset(&g, 0, sizeof(g));
+    g.q = q + q0 * ix->D;
+    g.nq = nqc;
+    g.qtiles = qtiles;
+    g.D = ix->D;
+    g.DP = DP;
+    g.rows_per_slab = rps;
+    g.part = part;
+    if (ix->NL_iso > 0) {   // isotropic rows: row-major fp32 means, 1/v folded into the coefficient
+      g.M = ix->iso_Mf;
+      g.nrows = ix->NL_iso;
+      g.coef = ca.coefL;
+      g.ncoef = NL;
+      g.coef_base = 0;
+      g.slab_off = 0;
+      HIPCHK(launch_grad_stream(g, s));
+    }
+    g.M = nullptr;
+    if (ix->NL_an > 0) {
+      g.A = ix->an_A;
+      g.B = ix->an_B;
+      g.ld = ix->ld_an;
+      g.nrows = ix->NL_an;
+      g.coef = ca.coefL;
+      g.ncoef = NL;
+      g.coef_base = ix->NL_iso;
+      g.slab_off = ns_iso;
+      HIPCHK(launch_grad_stream(g, s));
+    }
+    if (NI > 0) {
+      g.A = ix->int_A;
+      g.B = ix->int_B;
+      g.ld = ix->ld_int;
+      g.nrows = NI;
+      g.coef = ca.coefI;
+      g.ncoef = NI;
+      g.coef_base = 0;
+      g.slab_off = ns_iso + ns_an;
+      HIPCHK(launch_grad_stream(g, s));
+    }
+    HIPCHK(launch_grad_reduce(part, nslab, qtiles, nqc, DP, ix->D, grad_q + q0 * ix->D, s));
+  }
+  return CWQ_OK;
+}
+
 extern "C" int cwq_node_logprob(cwq_index* ix, const float* q, int64_t nq, int32_t full, float* out, void* stream) {
   if (!ix || (!q && nq > 0) || (!out && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
   if (nq == 0) return CWQ_OK;

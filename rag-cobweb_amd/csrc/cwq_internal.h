@@ -890,6 +890,41 @@ hipError_t launch_final(const float* X, const float* Mf, int DP, int nq, int K, 
                         const float* lkb, const int* lrb, const int* done, const IntChain* chain, int cat,
                         float dconst, hipStream_t s, const FwExpand* fx = nullptr);
 
+// ---- backward of cwq_rank_scores (cwq_grad.hip) ----
+// Coefficient pass: upstream gradients G [nq][n_sent] -> per-row / per-internal-node
+// coefficients, stored [query tile of 16][row][16].
+struct GradCoefArgs {
+  const float* G; int64_t n_sent; int nq, qtiles;
+  int NL, NL_iso, NI;
+  const int64_t* sent_ptr; const int64_t* sent_ids; const RowMeta* meta;
+  const int* leaf_a0; const int* leaf_a1; const int* leaf_b0; const int* leaf_b1;
+  const int* child_begin; const int* child_end; const float* w_int;
+  const int* lv; int nlev;    // host: level ranges [2 * l] = first, [2 * l + 1] = end
+  int P;                      // threads per (node, query): 16 (one node per workgroup) or 1
+  int nsplit;                 // pieces of a node's leaf-row ranges (cz lines)
+  float* coefL; float* hL;    // [qtiles][NL][16]: stream coefficient, parent's share invL g
+  float* cz;                  // [nsplit][qtiles][NI][16]
+  float* cI; float* coefI;    // [qtiles][NI][16]: c, w_int c
+};
+hipError_t launch_grad_coef(const GradCoefArgs& a, hipStream_t s);
+// One row class of the streaming reduction: isotropic rows (M row-major [nrows][DP], term
+// coef (x - mu)) or dim-major A / B [DP][ld] (term coef A (x A - B)); partial tiles
+// part[slab_off + slab][qtiles * 16][DP] for the valid queries.
+struct GradStreamArgs {
+  const float* q; int nq, qtiles, D, DP;
+  const float* M; const float* A; const float* B; int64_t ld;
+  int nrows, rows_per_slab;
+  const float* coef; int ncoef, coef_base;
+  float* part; int slab_off;
+};
+hipError_t launch_grad_stream(const GradStreamArgs& g, hipStream_t s);
+// out[q][d] = -sum over the slabs in index order, d < D
+hipError_t launch_grad_reduce(const float* part, int nslab, int qtiles, int nq, int DP, int D, float* out,
+                              hipStream_t s);
+// rows per slab for `weighted_rows` rows of stream (three slabs per CU, at least 256 rows):
+// a function of the index alone, so a query's gradient does not depend on the batch
+int grad_rows_per_slab(int64_t weighted_rows, int cus);
+
 // PCA + ICA whitening (cwq_whiten.hip): C[m][n] = sum_k (A[m][k] - ctr[k]) B[n][k] (/ denom[n])
 hipError_t launch_gemm_nt_f32(const float* A, int64_t M, int K, const float* ctr, const float* B, int N,
                               const float* denom, float* C, hipStream_t s);

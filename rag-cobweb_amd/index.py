@@ -211,13 +211,30 @@ class CobwebIndex:
         return {"direct": int(out[0]), "dense_lazy": int(out[1])}
 
     def close(self):
+        """Destroy the device index.  While an autograd graph still holds this index for a
+        pending backward (autograd._Pin), the destruction waits for the last such graph."""
+        if getattr(self, "_pins", 0) > 0:
+            self._close_pending = True
+            return
+        self._destroy()
+
+    def _destroy(self):
         if getattr(self, "_h", None) and self._h.value:
             self._L.cwq_index_destroy(self._h)
             self._h = ctypes.c_void_p()
 
+    def _pin(self):
+        self._pins = getattr(self, "_pins", 0) + 1
+
+    def _unpin(self):
+        self._pins -= 1
+        if self._pins == 0 and getattr(self, "_close_pending", False):
+            self._close_pending = False
+            self._destroy()
+
     def __del__(self):
         try:
-            self.close()
+            self._destroy()
         except Exception:
             pass
 
@@ -281,11 +298,34 @@ class CobwebIndex:
         return nodes, found, calls
 
     def rank_scores(self, q):
-        """All sentence scores (A8), [nq, n_sent]."""
+        """All sentence scores (A8), [nq, n_sent].  A tensor that requires grad (with grad
+        enabled) gets scores with autograd history (autograd.RankScores: the backward is
+        cwq_rank_scores_backward); the gradient arrives on q's own device and dtype."""
+        if torch.is_tensor(q) and q.requires_grad and torch.is_grad_enabled():
+            from .autograd import rank_scores_autograd
+            return rank_scores_autograd(self, q)
         q = self._queries(q)
         out = torch.empty((q.shape[0], self.n_sent), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             check(self._L.cwq_rank_scores(self._h, _ptr(q), q.shape[0], _ptr(out), _stream(self.device)))
+        return out
+
+    def rank_scores_backward(self, q, grad_out):
+        """Gradient of rank_scores with respect to the queries: grad_out [nq, n_sent] (the
+        upstream gradient of every score; columns of sentences that are not in the tree are
+        never read) -> [nq, dim] float32.  Needs nothing from the forward call; bit-identical
+        from run to run and for a query alone or in a batch."""
+        q = self._queries(q)
+        g = torch.as_tensor(grad_out, dtype=torch.float32)
+        if g.dim() == 1:
+            g = g[None, :]
+        if g.shape != (q.shape[0], self.n_sent):
+            raise ValueError(f"grad_out must be [{q.shape[0]}, {self.n_sent}]")
+        g = g.to(self.device).contiguous()
+        out = torch.empty((q.shape[0], self.dim), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._L.cwq_rank_scores_backward(self._h, _ptr(q), q.shape[0], _ptr(g), _ptr(out),
+                                                   _stream(self.device)))
         return out
 
     def node_logprob(self, q, full=False):

@@ -14,10 +14,13 @@ Differences (documented in DESIGN.md §6):
     key (CobwebTorchTree.py:243,285); the global random() stream is still advanced by
     the draws the reference makes and the retrieved leaves' lists are shuffled with it
     (CobwebWrapper.py:456), so add -> Basic query -> add builds the reference's tree;
-  * `cobweb_rank_scores` returns a tensor without autograd history (training
-    through the scores, src/training/cobweb_query_train.py, is out of scope);
+  * `cobweb_rank_scores` is differentiable with respect to a tensor embedding that
+    requires grad, as in the reference (the training loss of
+    src/training/cobweb_query_train.py:104-126 backpropagates into the query encoder);
+    the backward is a libcwq kernel (autograd.py), not torch autograd over node tensors;
   * batched entry points `cobweb_predict_batch` / `cobweb_categorize_batch` take a
-    [Q, D] query block and return id tensors.
+    [Q, D] query block and return id tensors; `cobweb_rank_scores_batch` is the
+    differentiable [Q, n_sentences] counterpart of `cobweb_rank_scores`.
 """
 import json
 import math
@@ -286,12 +289,21 @@ class CobwebWrapper:
         return self.cobweb_predict_indexed(input, k, return_ids, is_embedding)
 
     def cobweb_rank_scores(self, input, is_embedding=False):
-        """CobwebWrapper.py:267-294: [n_sentences] leaf scores (no autograd)."""
+        """CobwebWrapper.py:267-294: [n_sentences] leaf scores.  Differentiable: a tensor
+        embedding that requires grad (on any device) gets scores with a grad_fn; with
+        is_embedding=False the graph is cut, as by the reference's torch.tensor(emb)."""
         self.build_prediction_index()
         x = input.to(self.device) if is_embedding else self._embed(input, False)
         if len(self._leaf_to_path_indices) == 0:
             return torch.empty(0, device=self.device)
         return self._index.rank_scores(x.reshape(1, -1))[0]
+
+    def cobweb_rank_scores_batch(self, queries):
+        """[Q, D] queries -> [Q, n_sentences] scores, differentiable like cobweb_rank_scores:
+        one pass over the node means forward and one backward for the whole block (a training
+        step of 16 queries streams them once, not 16 times)."""
+        self.build_prediction_index()
+        return self._index.rank_scores(queries)
 
     def cobweb_predict(self, input, k=5, return_ids=False, is_embedding=False):
         """CobwebWrapper.py:435-461 ("Cobweb Basic"): best-first categorize with
