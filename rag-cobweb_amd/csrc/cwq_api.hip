@@ -2524,6 +2524,10 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
     g.n_rt = cuts[ph + 1] - cuts[ph];
     const std::vector<int>& up = cat ? ix->cat_uni_prefix : ix->tile_uni_prefix;
     g.all_uniform = up[cuts[ph + 1]] - up[cuts[ph]] == g.n_rt && !getenv("CWQ_FG_NO_ALLUNI");
+    // all-uniform Fast-key launches append raw records; the bucket pass evaluates their
+    // bounds (the categorize tables keep the in-kernel bounds: their key is min'ed with
+    // the bottleneck table per survivor)
+    g.raw = g.all_uniform && !cat;
     if (ix->timing) HIPCHK(hipEventRecord(ix->ev[5], s));
     unsigned long long* stamp_d = nullptr;
     const char* stamp_f = ph == nph - 1 ? getenv("CWQ_FG_STAMP") : nullptr;   // diagnostic builds
@@ -2555,8 +2559,11 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
         ix->t_ms[5] += e0;
       }
     }
-    HIPCHK(launch_bucket(rec, gctr, chunk_fill, rec_cap, rec_dir, dir_cap, kFgCapQ, qcnt, qover, crow, cu, cl,
-                         s));
+    if (g.raw)   // before launch_tighten: the records are tested against this launch's T
+      HIPCHK(launch_bucket_raw(g, kFgCapQ, qcnt, crow, cu, cl, s));
+    else
+      HIPCHK(launch_bucket(rec, gctr, chunk_fill, rec_cap, rec_dir, dir_cap, kFgCapQ, qcnt, qover, crow, cu, cl,
+                           s));
     if (ph + 1 < nph)
       HIPCHK(launch_tighten(nqc, K, kFgCapQ, qcnt, qover, cl, tl + (K - 1), 64, tlk, tr, tdone, gctr, s));
   }

@@ -312,7 +312,8 @@ hipError_t launch_welford_groups(const float* X, int D, const int64_t* order, co
 
 // bf16-MFMA candidate filter (cwq_mfma.hip)
 constexpr int kFgTile = 256;      // fgemm tile edge (queries and rows); operands are padded to it
-constexpr int kFgCap = 512;       // candidate records per tile (LDS staging)
+constexpr int kFgCap = 512;       // candidate records in the workgroup's LDS list (per tile; raw launches: carried
+                                  // from tile to tile and flushed from half full)
 constexpr int kFgChunk = 2048;    // record slots a workgroup claims at a time
 constexpr int kFgCapQ = 4096;     // candidate records per query
 constexpr int kFinalWideMaxQ = 256;   // final_kernel: workgroup per query up to this many queries
@@ -423,7 +424,9 @@ struct FgArgs {
                                           // 2: internal-node lp' bounds (dense lo/hi)
   int rt_off;                             // first row tile of this launch (filter phases)
   int all_uniform;                        // every row tile of the launch is uniform (TileF)
-  int qgroups, rgroups;                   // XCD split (qgroups * rgroups == 8)
+  int raw;                                // all-uniform filter launch that appends raw records {q, row, d, ex}:
+                                          // bucket_raw_kernel turns them into bounds (not the categorize tables)
+  int qgroups, rgroups;                  // XCD split (qgroups * rgroups == 8)
   int order;                              // tile order: 0 static q-fastest, 1 static r-fastest, 2 dynamic
   int* tctr;                              // order 2: per-XCD tile counters [8] (zeroed before the launch)
   int dbg;                                // ablation (perf experiments only): 1 no operand loads, 2 no epilogue
@@ -453,7 +456,7 @@ struct FgArgs {
   float root_w, root_ld;                  // mode 2: the root's level weight and logdet
   int64_t ldlb;
   int lbg;                                // sample: rows per lower-bound group (1 or 4)
-  int4* rec;                              // filter: appended records {q, row, u, l}
+  int4* rec;                              // filter: appended records {q, row, u, l} (raw: {q, row, d, ex})
   int64_t rec_cap;                        // record slots (a multiple of kFgChunk)
   int* gctr;                              // [0] chunks claimed, [1] direct records (zeroed before the launch)
   int4* rec_dir;                          // direct records (a tile with more than kFgCap)
@@ -856,6 +859,9 @@ hipError_t launch_tile_prange(const float* P, const float* Phi, int64_t ldP, int
                               int n_rt, float2* pmm, int64_t ldq, hipStream_t s, const PathB* pb = nullptr);
 hipError_t launch_bucket(const int4* rec, const int* gctr, const int* chunk_fill, int64_t rec_cap, const int4* rec_dir,
                          int dir_cap, int capq, int* qcnt, int* qover, int* crow, float* cu, float* cl, hipStream_t s);
+// the same for a raw launch (a.raw): the records' bounds are evaluated here, against the
+// launch's own thresholds a.T (so before the next launch_tighten)
+hipError_t launch_bucket_raw(const FgArgs& a, int capq, int* qcnt, int* crow, float* cu, float* cl, hipStream_t s);
 // lkb/lrb [nq][64] and done [nq] carry each query's top-K candidate lower bounds between
 // the tighten calls and into final (done must start at 0); zero16[0..15] is cleared
 // (the filter's record and tile-claim counters for the next launch)

@@ -630,12 +630,13 @@ constexpr int FK = 32;            // K per LDS stage
 constexpr int FNBUF = 4;          // LDS stage ring: 3 stages in flight while one is consumed
 constexpr int FSTAGE = 2 * FT * FK * 2;   // bytes of one stage (A + B images) = 32 KiB
 constexpr int OFF_QV = FNBUF * FSTAGE;    // float  [FT]   pretest query terms
-constexpr int OFF_QI = OFF_QV + FT * 4;   // float4 [FT]   {|x'|^2, a, c, T}
+constexpr int OFF_QI = OFF_QV + FT * 4;   // float4 [FT]   {|x'|^2, a, c, T} (RAW: float [FT], odd tiles' pretest terms)
 constexpr int OFF_PI = OFF_QI + FT * 16;  // float  [FT]   pi of the tile's parent (upper bound)
 constexpr int OFF_PL = OFF_PI + FT * 4;   // float  [FT]   its lower bound (= pi when exact)
 constexpr int OFF_REC = OFF_PL + FT * 4;  // int4   [kFgCap] record staging
-constexpr int OFF_CNT = OFF_REC + kFgCap * 16;   // int[16]: count, chunk, fill, flush scratch, claim
-constexpr int FLDS = OFF_CNT + 64;
+constexpr int OFF_CNT = OFF_REC + kFgCap * 16;   // int[32]: count, chunk, fill, flush scratch, claim; [16 + wave]:
+                                                 // RAW, records in the wave's overflow area
+constexpr int FLDS = OFF_CNT + 128;
 
 
 // Internal node i, query x (mode 2): lp'(i) = -0.5 (logdet_i + S), S = sum_d w_d (x_d - mu_d)^2
@@ -694,9 +695,9 @@ __device__ __forceinline__ int fg_count(const FgArgs& a, int xcd) {
 #define FG_STAMP 0   // diagnostic builds: s_memtime stamps of the ping-pong loop (FgArgs::stamp)
 #endif
 #ifndef FG_LEAN
-#define FG_LEAN 1   // filter tiles without records skip the flush's second barrier and the per-tile third one
-#endif
-#define FG_CSLOT (FG_LEAN && MODE == 0 && (tile_no & 1) ? 9 : 0)
+#define FG_LEAN 1   // in-kernel-bounds filter tiles (not RAW) without records skip the flush's second barrier
+#endif              // and the per-tile third one: their record counter alternates between two slots
+#define FG_CSLOT (FG_LEAN && !RAW && MODE == 0 && (tile_no & 1) ? 9 : 0)
 // 16-B chunk position of logical chunk 0 in row r of a stage image (a permutation of the
 // row's 4 chunks, XORed with the chunk index), chosen so that the ds_read_b128 fragment
 // reads of a wave are bank-conflict free: for 16x16x32 lane l reads row l&15, chunk
@@ -738,11 +739,39 @@ __device__ __forceinline__ TileF fg_tile_const(const TileF* p, int i) {
   return t;
 }
 
+// Raw record {q, row, d, ex} of an all-uniform launch -> its rigorous bounds, from the same
+// inputs and with the same fg_bounds2 as the in-kernel path: qinfo[q], rf[row], the row
+// tile's parent prefix x invL (as the tile setup forms it).  True when the record is a
+// candidate: u >= T[q], the threshold the launch runs with.
+__device__ __forceinline__ bool fg_raw_bounds(const FgArgs& a, int q, int row, float d, float ex, float& u,
+                                              float& lo) {
+  const RowF f = a.rf[row];
+  if (f.par < -1) return false;
+  const TileF tf = a.tf[row / kFgTile];
+  float Pq = 0.f, Pql = 0.f;
+  if (tf.par >= 0) {
+    if (a.pb.dot) {
+      pathb_bounds(a.pb, q, tf.par, Pql, Pq);
+    } else {
+      Pq = (a.Phi ? a.Phi : a.P)[pidx(a.ldP, a.pT, q, tf.par)];
+      Pql = a.P[pidx(a.ldP, a.pT, q, tf.par)];
+    }
+  }
+  // (__fmul_rn: the rounded products the tile setup stores, never contracted into fg_bounds2's sums)
+  const float pi = __fmul_rn(Pq, tf.invL), pl = __fmul_rn(Pql, tf.invL);
+  fg_bounds2(d, ex, a.qinfo[q], f, pi, pl, a.eps_n, a.slack, u, lo);
+  return u >= a.T[(size_t)q * a.ldT];
+}
+
 // MODE 0: filter pass (records), MODE 1: threshold-sample pass (dense lower bounds);
 // separate instantiations so profiles tell them apart and each drops the other's code.
 // ALLUNI: every row tile of the launch is uniform (flat trees): the per-element generic
 // bound path is compiled out.
-template <int MODE, bool ALLUNI>
+// RAW (with ALLUNI, Fast-key tables): the epilogue appends the pretest survivors as raw
+// records {q, row, d, ex} straight from the accumulators and bucket_raw_kernel evaluates
+// fg_bounds2 and u >= T; the record list is carried from tile to tile and the setup
+// barrier is the tile's only workgroup barrier outside the K loop (see "RAW ordering").
+template <int MODE, bool ALLUNI, bool RAW = false>
 __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ Xb, const __bf16* __restrict__ Mb,
                                                     const FgArgs a) {
   __shared__ __attribute__((aligned(16))) char smem[FLDS];
@@ -774,6 +803,46 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
   };
   int4* s_rec = reinterpret_cast<int4*>(smem + OFF_REC);
   int* s_cnt = reinterpret_cast<int*>(smem + OFF_CNT);
+  static_assert(!RAW || (MODE == 0 && ALLUNI), "raw records: all-uniform filter launches only");
+  static_assert(kFgCap == 512, "the record flush copies one record per thread");
+  // RAW: records of the carried list -> the global append buffer, in chunks of kFgChunk
+  // slots owned by this workgroup.  Called by every thread with the same cnt, read after a
+  // workgroup barrier that follows every append (the next tile's setup barrier, or the
+  // barrier at kernel exit).  Records that found no chunk mark their own query for the
+  // exact re-run (the list holds records of several tiles).
+  auto flush_records = [&](int cnt) {
+    const int n = min(cnt, kFgCap);
+    if (tid == 0) {
+      int chunk = s_cnt[1], fill = s_cnt[2];
+      int n1 = chunk >= 0 ? min(n, kFgChunk - fill) : 0;
+      int base1 = chunk * kFgChunk + fill, base2 = 0, nw = n;
+      fill += n1;
+      if (n > n1) {
+        if (chunk >= 0) a.chunk_fill[chunk] = fill;
+        const int c2 = atomicAdd(a.gctr, 1);
+        if ((int64_t)(c2 + 1) * kFgChunk > a.rec_cap) {   // buffer full: the rest is lost
+          chunk = -1;
+          fill = 0;
+          nw = n1;
+        } else {
+          chunk = c2;
+          fill = n - n1;
+          base2 = c2 * kFgChunk;
+        }
+      }
+      s_cnt[1] = chunk;
+      s_cnt[2] = fill;
+      s_cnt[3] = base1;
+      s_cnt[4] = n1;
+      s_cnt[5] = nw;
+      s_cnt[6] = base2;
+    }
+    __syncthreads();   // F: the bookkeeping is visible, and every thread has read cnt
+    const int nw = s_cnt[5], n1 = s_cnt[4];
+    if (tid < nw) a.rec[tid < n1 ? s_cnt[3] + tid : s_cnt[6] + (tid - n1)] = s_rec[tid];
+    else if (tid < n) a.qover[s_rec[tid].x] = 1;
+    if (tid == 0) s_cnt[0] = 0;
+  };
   // per-lane source offsets of the two 16-row pieces a wave stages per operand
   uint32_t loff[2];
 #pragma unroll
@@ -821,19 +890,22 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
   (void)tile_no;
   fg_decode(a, xcd, i, qt, rt);
   if (tid == 0) {
-    s_cnt[0] = 0;    // records of the current tile (FG_LEAN: even tiles; odd tiles count in [9])
+    s_cnt[0] = 0;    // records of the current tile (FG_LEAN: even tiles; odd tiles count in [9]); RAW: of
+                     // the list carried from tile to tile
     s_cnt[9] = 0;
     s_cnt[1] = -1;   // owned chunk
     s_cnt[2] = 0;    // its fill
   }
+  if (RAW && lane == 0) s_cnt[16 + wave] = 0;   // (read and written by this wave only)
   f32x4 acc[8][4];
 #if FG_STAMP
-  // diagnostic: per-tile timestamps of wave 0 of workgroups 0..63, tiles 0..15: [wg][tile][4]
-  // (setup start, setup barrier passed, K loop done, epilogue done) after the stage stamps
-  unsigned long long* tsp = (a.stamp && blockIdx.x < 64 && tid == 0) ? a.stamp + 16384 + (size_t)blockIdx.x * 64 : nullptr;
+  // diagnostic: per-tile timestamps of wave 0 of workgroups 0..63, tiles 0..15: [wg][tile][8]
+  // (0 setup start, 1 setup barrier passed, 2 K loop done, 3 fast-path test done, 4 slow
+  // path done, 5 flush barrier passed, 6 flush / epilogue done) after the stage stamps
+  unsigned long long* tsp = (a.stamp && blockIdx.x < 64 && tid == 0) ? a.stamp + 16384 + (size_t)blockIdx.x * 128 : nullptr;
 #define FG_TS(k)                                                                  \
   do {                                                                            \
-    if (tsp && tile_no < 16) tsp[tile_no * 4 + (k)] = __builtin_amdgcn_s_memtime(); \
+    if (tsp && tile_no < 16) tsp[tile_no * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
 #else
 #define FG_TS(k) \
@@ -876,12 +948,16 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb) {
       const int r = r0 + wr * 64 + jb * 16 + r16;
-      R0[jb] = (uni && r < a.nrows) ? a.rf[r].R0 : 0.f;
+      // RAW: rows past the end can never pass the pretest (the epilogue tests nothing else)
+      R0[jb] = (uni && r < a.nrows) ? a.rf[r].R0 : RAW ? -CWQ_INF : 0.f;
     }
+    // RAW: the pretest terms alternate between two buffers by tile parity (the second one
+    // in the s_qi region, which RAW tiles do not use)
+    float* const s_qvt = RAW && (tile_no & 1) ? reinterpret_cast<float*>(smem + OFF_QI) : s_qv;
     if (tid < FT) {
       const float T = Tq;
       qi.w = T;
-      s_qi[tid] = qi;
+      if (!RAW) s_qi[tid] = qi;
       // pretest query term for a parent prefix pi (smaller = more permissive)
       auto qv_of = [&](float pi) {
         const float tpg = (T - pi) / tf.g;
@@ -911,10 +987,12 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
           }
         }
       }
-      s_pi[tid] = pi;
-      s_pl[tid] = uni ? Pql * tf.invL : 0.f;
+      if (!RAW) {   // (RAW: bucket_raw_kernel takes qinfo, T and the parent prefix from memory)
+        s_pi[tid] = pi;
+        s_pl[tid] = uni ? Pql * tf.invL : 0.f;
+      }
       if (MODE == 2) s_pl[tid] = qs < a.nq ? a.root_w * (-0.5f * (a.root_ld + a.Sroot[qs])) : 0.f;   // exact root P
-      s_qv[tid] = qv;
+      s_qvt[tid] = qv;
     }
     if (dyn && tid == 0) s_cnt[8] = claimv;   // the tile after this one
     __syncthreads();   // stage 0 landed, setup visible
@@ -922,12 +1000,36 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     if (dyn) next_i = __builtin_amdgcn_readfirstlane(s_cnt[8]);   // uniform: scalar tile loads
     // FG_LEAN: the previous tile's record counter (every thread read it before this
     // barrier) is cleared for the tile after this one
-    if (FG_LEAN && MODE == 0 && tid == 0 && tile_no > 0) s_cnt[(tile_no & 1) ? 0 : 9] = 0;
+    if (FG_LEAN && !RAW && MODE == 0 && tid == 0 && tile_no > 0) s_cnt[(tile_no & 1) ? 0 : 9] = 0;
+    // RAW ordering.  S(n) is the setup barrier above of this workgroup's n-th tile, E(n)
+    // its epilogue; a wave goes from E(n) straight into the setup of tile n+1.  Every
+    // s_barrier is workgroup-wide and the K loop holds at least 8 of them, so a wave is in
+    // E(n) only after all waves passed S(n) and left everything before the K loop, and all
+    // waves reach S(n+1) only after their own E(n).
+    //  s_qv[parity]: written by setup n (before S(n)), read by the accumulator init and
+    //    E(n) (after S(n): RAW ok).  Its next writer is setup n+2, after S(n+1), which
+    //    every wave reaches after its E(n) (WAR ok); setup n+1 writes the other buffer.
+    //  s_cnt[8] (next tile claim): written by thread 0 in setup n, read by all right after
+    //    S(n); rewritten in setup n+1, which wave 0 reaches through K loop n (WAR ok).
+    //  s_cnt[0], s_rec (carried record list): appended to by E(n) with LDS atomics.  The
+    //    count read here after S(n) holds all of E(n-1) and is the same for every thread:
+    //    the next append is in E(n), behind the K loop's barriers.  The flush reads s_rec,
+    //    and thread 0 clears the count after barrier F, which follows every thread's read
+    //    of it; both precede the K loop's barriers and so E(n)'s appends (WAR ok).
+    //  s_cnt[1..7] (chunk bookkeeping): written by thread 0 before F, read by all after F
+    //    and before the K loop; the next flush is at least one K loop later.
+    //  Stage buffers: E(n) uses the buffer just consumed only when the list is full (the
+    //    wave's overflow area), each wave its own 4 KiB, before it arrives at S(n+1); the
+    //    DMA into that buffer is issued in K loop n+1, after S(n+1) (WAR ok).
+    if (RAW) {
+      const int cnt = s_cnt[0];
+      if (cnt >= kFgCap / 2) flush_records(cnt);   // at least half full: a tile then has kFgCap / 2 slots left
+    }
     // ---- accumulator init: R_r - Qv_q on uniform tiles, 0 otherwise ----
     // 16x16x32 layout: acc[ib][jb][j] = C[query wq*128 + ib*16 + 4*c16 + j][row wr*64 + jb*16 + r16]
 #pragma unroll
     for (int ib = 0; ib < 8; ++ib) {
-      const float4 qv4 = uni ? *reinterpret_cast<const float4*>(s_qv + wq * 128 + ib * 16 + 4 * c16)
+      const float4 qv4 = uni ? *reinterpret_cast<const float4*>(s_qvt + wq * 128 + ib * 16 + 4 * c16)
                              : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int jb = 0; jb < 4; ++jb) {
@@ -1155,7 +1257,73 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
           anyb[jb][hf] = __ballot(m >= 0.f) != 0;
           any = any || anyb[jb][hf];
         }
+      FG_TS(3);
       if (!any) goto flush;
+      if (RAW) {
+        // flagged blocks: the pretest survivors (acc >= 0) go to the record list straight
+        // from the accumulators, as {q, row, d, ex}: d the dot without the pretest terms
+        // and ex the rounding the accumulator init added to it (fg_bounds2's eextra).  No
+        // barrier and, while the list has room, no global load; LDS is read for s_qv only.
+        // Padding rows and queries never get here (R0 = -inf / qv = +inf).
+        // wrec, the wave's overflow area for a full list: its 4 KiB of the stage buffer
+        // just consumed (the other instantiations' wsc), free until a wave issues the next
+        // tile's first K step -- after the next setup barrier, which this wave reaches
+        // after this epilogue.
+        int4* const wrec = reinterpret_cast<int4*>(wsc);
+        bool ovf = false;
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+          const int r = r0 + wr * 64 + jb * 16 + r16;
+#pragma unroll
+          for (int ib = 0; ib < 8; ++ib) {
+            if (!anyb[jb][ib >> 2]) continue;
+            const int ql = wq * 128 + ib * 16 + 4 * c16;
+            const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
+            const float qvj[4] = {qv4.x, qv4.y, qv4.z, qv4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float d0 = acc[ib][jb][j];
+              if (d0 >= 0.f) {
+                const float init = R0[jb] - qvj[j];
+                const float d = d0 - init;
+                const float ex = a.gamma * fabsf(init) + 0x1p-23f * (fabsf(d0) + fabsf(init));
+                const int4 rv = make_int4(q0 + ql + j, r, __float_as_int(d), __float_as_int(ex));
+                const int slot = atomicAdd(&s_cnt[0], 1);
+                if (slot < kFgCap) {
+                  s_rec[slot] = rv;
+                } else {   // list full: to the wave's overflow area (4 values x 64 lanes fit)
+                  wrec[atomicAdd(&s_cnt[16 + wave], 1)] = rv;
+                  ovf = true;
+                }
+              }
+            }
+            if (__builtin_expect(__any(ovf), 0)) {
+              // Dense tiles, and data on which the pretest's margins pass far more than
+              // u >= T does: the rigorous test here (a rolled loop, global loads), so that
+              // the direct region takes candidates only, as on the in-kernel path.
+              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+              __builtin_amdgcn_wave_barrier();
+              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+              const int no = s_cnt[16 + wave];
+#pragma unroll 1
+              for (int k = lane; k < no; k += 64) {
+                const int4 rv = wrec[k];
+                float u, lo;
+                if (fg_raw_bounds(a, rv.x, rv.y, __int_as_float(rv.z), __int_as_float(rv.w), u, lo)) {
+                  const int gs = atomicAdd(&a.gctr[1], 1);
+                  if (gs < a.dir_cap) a.rec_dir[gs] = rv;
+                  else a.qover[rv.x] = 1;
+                }
+              }
+              __builtin_amdgcn_wave_barrier();   // the area is read before it is refilled
+              if (lane == 0) s_cnt[16 + wave] = 0;
+              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+              ovf = false;
+            }
+          }
+        }
+        goto flush;
+      }
     } else {
 #pragma unroll
       for (int jb = 0; jb < 4; ++jb) anyb[jb][0] = anyb[jb][1] = true;
@@ -1260,12 +1428,14 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
         }
     }
   flush:
-    if (MODE == 0) {
+    FG_TS(4);
+    if (MODE == 0 && !RAW) {
       // records -> global append buffer, in chunks of kFgChunk slots owned by this
       // workgroup (one atomic per chunk, not per tile).  This barrier also ends every
       // epilogue LDS read of the tile (wsc, s_qi/s_qv/s_pi), so the next setup may
       // rewrite them; a tile without records skips the rest (uniform: all read cnt here).
       __syncthreads();
+      FG_TS(5);
       const int cnt = s_cnt[FG_CSLOT];
       const int n = min(cnt, kFgCap);
       if (FG_LEAN && n == 0) goto next_tile;
@@ -1305,15 +1475,20 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     }
   next_tile:
     i = next_i;
-    FG_TS(3);
+    FG_TS(6);
     ++tile_no;
     if (i >= ntl) break;
     if (!dyn) next_i = i + nw_x;
     fg_decode(a, xcd, i, qt, rt);
-    if (MODE != 0 || !FG_LEAN) {
+    if (!RAW && (MODE != 0 || !FG_LEAN)) {
       __syncthreads();   // epilogue LDS reads done before the next setup rewrites them
       if (tid == 0) s_cnt[0] = 0;
     }
+  }
+  if (RAW) {   // the carried records of the last tiles
+    __syncthreads();   // every wave's last epilogue is done
+    const int cnt = s_cnt[0];
+    if (cnt > 0) flush_records(cnt);
   }
   if (MODE == 0 && tid == 0 && s_cnt[1] >= 0) a.chunk_fill[s_cnt[1]] = s_cnt[2];
 }
@@ -1336,6 +1511,11 @@ hipError_t launch_fgemm(const void* Xb, const void* Mb, const FgArgs& a, int n_w
                        (const __bf16*)Mb, a);
   else if (a.mode == 2)
     hipLaunchKernelGGL((fgemm_kernel<2, false>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
+                       (const __bf16*)Mb, a);
+  else if (a.raw && !a.all_uniform)
+    return hipErrorInvalidValue;
+  else if (a.raw)
+    hipLaunchKernelGGL((fgemm_kernel<0, true, true>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
                        (const __bf16*)Mb, a);
   else if (a.all_uniform)
     hipLaunchKernelGGL((fgemm_kernel<0, true>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
@@ -1377,6 +1557,36 @@ __global__ __launch_bounds__(256) void bucket_kernel(const int4* __restrict__ re
     if ((int)(g % kFgChunk) < chunk_fill[g / kFgChunk]) bucket_one(rec[g], capq, qcnt, qover, crow, cu, cl);
   const int n_dir = min(gctr[1], dir_cap);
   for (int64_t d = g0; d < n_dir; d += stride) bucket_one(rec_dir[d], capq, qcnt, qover, crow, cu, cl);
+}
+
+// Raw records {q, row, d, ex} of an all-uniform launch (fgemm_kernel<0, true, true>): the
+// rigorous bounds are evaluated here (fg_raw_bounds) and the record is kept when u >= T[q],
+// the threshold the launch ran with (this pass runs before tighten_kernel raises it).
+__device__ __forceinline__ void bucket_raw_one(const FgArgs& a, const int4 r, int capq, int* qcnt, int* crow,
+                                               float* cu, float* cl) {
+  const int q = r.x, row = r.y;
+  if ((unsigned)q >= (unsigned)a.nq || (unsigned)row >= (unsigned)a.nrows) return;
+  float u, lo;
+  if (fg_raw_bounds(a, q, row, __int_as_float(r.z), __int_as_float(r.w), u, lo))
+    bucket_one(make_int4(q, row, __float_as_int(u), __float_as_int(lo)), capq, qcnt, a.qover, crow, cu, cl);
+}
+
+__global__ __launch_bounds__(256) void bucket_raw_kernel(const FgArgs a, int capq, int* qcnt, int* crow, float* cu,
+                                                         float* cl) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t g0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t n_rec = min((int64_t)a.gctr[0] * kFgChunk, a.rec_cap);
+  for (int64_t g = g0; g < n_rec; g += stride)
+    if ((int)(g % kFgChunk) < a.chunk_fill[g / kFgChunk]) bucket_raw_one(a, a.rec[g], capq, qcnt, crow, cu, cl);
+  const int n_dir = min(a.gctr[1], a.dir_cap);
+  for (int64_t d = g0; d < n_dir; d += stride) bucket_raw_one(a, a.rec_dir[d], capq, qcnt, crow, cu, cl);
+}
+
+hipError_t launch_bucket_raw(const FgArgs& a, int capq, int* qcnt, int* crow, float* cu, float* cl, hipStream_t s) {
+  const int64_t n = a.rec_cap + a.dir_cap;
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(bucket_raw_kernel, dim3(grid), dim3(256), 0, s, a, capq, qcnt, crow, cu, cl);
+  return hipGetLastError();
 }
 
 hipError_t launch_bucket(const int4* rec, const int* gctr, const int* chunk_fill, int64_t rec_cap, const int4* rec_dir,

@@ -14,14 +14,28 @@ for g in range(2):
           f"mfma {np.median(d[:, 2]):.0f}  wait-out {np.median(d[:, 3]):.0f}  (median cycles; total "
           f"{np.median(d.sum(-1)):.0f})")
 
-# per-tile stamps (wave 0 of workgroups 0..63, tiles 0..15): setup, K loop, epilogue, gap
-t = np.fromfile(sys.argv[1], dtype=np.uint64)[16384:16384 + 64 * 64].reshape(64, 16, 4).astype(np.int64)
-okt = (t[..., 0] > 0) & (t[..., 3] > 0)
+# per-tile stamps (wave 0 of workgroups 0..63, tiles 0..15): setup start, setup barrier
+# passed, K loop done, fast-path test done, slow path done, flush barrier passed, flush /
+# epilogue done.  A stamp the tile did not pass (no uniform test, no flush barrier) is
+# filled from its predecessor, so that part reads 0.
+t = np.fromfile(sys.argv[1], dtype=np.uint64)[16384:16384 + 64 * 128].reshape(64, 16, 8).astype(np.int64)[..., :7]
+for k in range(3, 6):
+    t[..., k] = np.where(t[..., k] > 0, t[..., k], t[..., k - 1])
+okt = (t[..., 0] > 0) & (t[..., 6] > 0)
 sel = t[okt]
 if len(sel):
     d = np.diff(sel, axis=-1)
-    gap = (t[:, 1:, 0] - t[:, :-1, 3])[okt[:, 1:] & okt[:, :-1]]
-    tot = np.median(d.sum(-1)) + (np.median(gap) if len(gap) else 0)
+    gap = (t[:, 1:, 0] - t[:, :-1, 6])[okt[:, 1:] & okt[:, :-1]]
+    mgap = np.median(gap) if len(gap) else 0
+    epi = sel[:, 6] - sel[:, 2]
+    tot = np.median(sel[:, 6] - sel[:, 0]) + mgap
     print(f"tiles: n={len(sel)}  setup {np.median(d[:, 0]):.0f}  K loop {np.median(d[:, 1]):.0f}  "
-          f"epilogue {np.median(d[:, 2]):.0f}  gap to next {np.median(gap) if len(gap) else 0:.0f}  "
+          f"epilogue {np.median(epi):.0f}  gap to next {mgap:.0f}  "
           f"(median s_memtime ticks; K loop share {np.median(d[:, 1]) / tot:.3f})")
+    names = ["fast-path test", "slow path", "flush barrier wait", "flush"]
+    print("epilogue of wave 0: " + "  ".join(
+        f"{n} median {np.median(d[:, 2 + i]):.0f} mean {np.mean(d[:, 2 + i]):.0f}" for i, n in enumerate(names)))
+    slow = d[:, 3] > 200   # wave 0 itself took the slow path
+    print(f"  wave 0 took the slow path in {slow.mean():.2f} of tiles"
+          + (f" (median {np.median(d[slow, 3]):.0f} there)" if slow.any() else "")
+          + f"; tiles that flushed records: {(d[:, 5] > 200).mean():.2f}")
