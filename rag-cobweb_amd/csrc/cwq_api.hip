@@ -114,6 +114,7 @@ struct cwq_index {
   // call: 0 not yet, 1 built, -1 off (CWQ_STREAM_I8=0, DPB % 64, or too little free memory)
   int8_t* iso_Mq = nullptr;
   RowF* iso_rf8 = nullptr;
+  TileF* iso_tf8 = nullptr;   // iso_tf with the int8 tile maxima (the batch filter's int8 launches)
   int i8_state = 0;
   std::vector<int> tile_uni_prefix;   // prefix counts of uniform row tiles (all_uniform per launch range)
   int n_multi_tiles = 0;              // tiles with several parents (TileF uniform 2)
@@ -211,6 +212,7 @@ struct cwq_index {
   bool timing = false;
   int filter = -1;   // cwq_set_filter
   int n_fg_launch = 0;   // filter launches of the last chunk (timing report)
+  int n_fg_i8 = 0;       // of the call's filter launches (all chunks), those on the int8 operands
   hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   float t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // workspace.  Every query call carves its buffers from `ws`; the call's kernels may
@@ -2059,22 +2061,52 @@ bool use_stream(const cwq_index* ix, int64_t nq, int k) {
 // is built by cwq_index_create when the policy holds there; a call that forces it on an
 // index created without it builds it then (A/B and test use only).
 constexpr int64_t kI8MinBytes = (int64_t)384 << 20;
-bool ensure_i8(cwq_index* ix, hipStream_t s) {
-  const char* e = getenv("CWQ_STREAM_I8");
-  if ((e && *e && atoi(e) == 0) || ix->grp_mode) return false;   // the int8 rows are root-centred
-  if (!(e && *e && atoi(e) == 1) && (int64_t)ix->NL_iso * ix->DPB < kI8MinBytes) return false;
+// The panel with its row and tile constants, whatever its size (the policies are the
+// callers'): built once per index; false when it cannot be (no room, group-centred rows).
+bool build_i8(cwq_index* ix, hipStream_t s) {
+  if (ix->grp_mode) return false;   // the int8 rows are root-centred
   if (ix->i8_state) return ix->i8_state > 0;
   ix->i8_state = -1;
-  if (ix->DPB % 64 || !ix->iso_Mf || !ix->iso_rf) return false;
-  const size_t need = (size_t)ix->ld_f * ix->DPB + (size_t)ix->ld_f * sizeof(RowF);
+  if (ix->DPB % 64 || !ix->iso_Mf || !ix->iso_rf || !ix->iso_tf) return false;
+  const size_t n_rt = (size_t)(ix->ld_f / kFgTile);
+  const size_t need = (size_t)ix->ld_f * ix->DPB + (size_t)ix->ld_f * sizeof(RowF) + n_rt * sizeof(TileF);
   size_t fr = 0, tot = 0;
   if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < need + std::max<size_t>((size_t)4 << 30, tot / 20)) return false;
-  if (ix->alloc(&ix->iso_Mq, (size_t)ix->ld_f * ix->DPB) || ix->alloc(&ix->iso_rf8, (size_t)ix->ld_f)) return false;
+  if (ix->alloc(&ix->iso_Mq, (size_t)ix->ld_f * ix->DPB) || ix->alloc(&ix->iso_rf8, (size_t)ix->ld_f) ||
+      ix->alloc(&ix->iso_tf8, n_rt))
+    return false;
   if (launch_rows_i8(ix->iso_Mf, ix->DP, ix->D, ix->iso_c, ix->DPB, ix->ld_f, ix->iso_rf, ix->iso_Mq, ix->iso_rf8, s) !=
-      hipSuccess)
+          hipSuccess ||
+      launch_tiles_i8(ix->iso_tf, ix->iso_rf8, (int)n_rt, ix->iso_tf8, s) != hipSuccess)
     return false;
   ix->i8_state = 1;
   return true;
+}
+bool ensure_i8(cwq_index* ix, hipStream_t s) {
+  const char* e = getenv("CWQ_STREAM_I8");
+  if ((e && *e && atoi(e) == 0) || ix->grp_mode) return false;
+  if (!(e && *e && atoi(e) == 1) && (int64_t)ix->NL_iso * ix->DPB < kI8MinBytes) return false;
+  return build_i8(ix, s);
+}
+
+// The batch filter's int8 launches (fgemm_kernel<0, true, true, true>): the
+// first filter phase that takes the int8 operands, nph for none.  By default the phases that
+// start at or past a quarter of the row tiles, on an index that has its int8 panel: the bf16
+// launches before them have raised T, so the wider int8 bounds pass few candidates
+// (profiles/fgi8_model_c3.log).  CWQ_FG_I8 (read per call; tests and in-process A/Bs):
+// negative: off; n >= 0: from phase n on, building the panel at any size.
+// A launch then takes them only when it is raw (all-uniform, Fast key).
+int fg_i8_from(cwq_index* ix, const int* cuts, int nph, bool cat, bool ib, hipStream_t s) {
+  if (cat || ib || ix->grp_mode || ix->DPB % 64) return nph;
+  const char* e = getenv("CWQ_FG_I8");
+  if (e && *e) {
+    const int v = atoi(e);
+    return v >= 0 && build_i8(ix, s) ? std::min(v, nph) : nph;
+  }
+  if (ix->i8_state <= 0) return nph;
+  for (int ph = 1; ph < nph; ++ph)   // (never the first launch: it runs on the sample threshold)
+    if (cuts[ph] >= cuts[nph] / 4) return ph;
+  return nph;
 }
 
 // CWQ_SELECT_UNFUSED=1: the per-call path keeps select_kernel (and sb_prep) -- A/B only
@@ -2411,7 +2443,8 @@ struct IsoFilter {
 };
 
 size_t iso_filter_bytes_per_query(const cwq_index* ix, int n_rt) {
-  return (size_t)ix->DPB * 2 + 16 + (size_t)ix->ld_s * 4 + 64 * 8 + (size_t)kFgCapQ * 12 + 32 +
+  return (size_t)ix->DPB * 2 + 16 + (size_t)ix->DPB + 16 +   // (the int8 query and its info)
+         (size_t)ix->ld_s * 4 + 64 * 8 + (size_t)kFgCapQ * 12 + 32 +
          (size_t)(rec_per_q(ix) + dir_per_q(ix)) * 16 + 64 + ((size_t)2 * ix->cus * kFgChunk * 16) / 256 +
          (ix->n_multi_tiles ? (size_t)n_rt * 8 : 0) + 4 + 64 * 4;
 }
@@ -2425,6 +2458,8 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
   const int n_qt = (int)(nqf / kFgTile);
   uint16_t* Xb = b.take<uint16_t>((size_t)nqf * ix->DPB);
   float4* qinfo = b.take<float4>(nqf);
+  int8_t* Xq = b.take<int8_t>((size_t)nqf * ix->DPB);   // the int8 launches' query side
+  float4* qinfo8 = b.take<float4>(nqf);
   float* lb = b.take<float>((size_t)nqf * ix->ld_s + 4096);
   float* tl = b.take<float>((size_t)nqf * 64);
   int* tr = b.take<int>((size_t)nqf * 64);
@@ -2519,6 +2554,11 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
   int cuts[6] = {0, n_rt, n_rt, n_rt, n_rt, n_rt};
   const int nph = fg_phase_cuts(n_rt, cuts);
   ix->n_fg_launch = nph;
+  const int i8_from = fg_i8_from(ix, cuts, nph, cat, ib, s);
+  bool i8_prepped = false;   // the int8 query side: once per chunk, before the first launch that reads it
+  g.qinfo8 = qinfo8;
+  g.rf8 = ix->iso_rf8;
+  g.tf8 = ix->iso_tf8;
   for (int ph = 0; ph < nph; ++ph) {
     g.rt_off = cuts[ph];
     g.n_rt = cuts[ph + 1] - cuts[ph];
@@ -2528,6 +2568,12 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
     // bounds (the categorize tables keep the in-kernel bounds: their key is min'ed with
     // the bottleneck table per survivor)
     g.raw = g.all_uniform && !cat;
+    g.i8 = g.raw && ph >= i8_from;   // (fg_i8_from)
+    if (g.i8 && !i8_prepped) {
+      HIPCHK(launch_query_prep_i8(qsrc, nqc, ix->D, ix->iso_c, ix->DPB, nqf, Xq, qinfo8, s));
+      i8_prepped = true;
+    }
+    ix->n_fg_i8 += g.i8;
     if (ix->timing) HIPCHK(hipEventRecord(ix->ev[5], s));
     unsigned long long* stamp_d = nullptr;
     const char* stamp_f = ph == nph - 1 ? getenv("CWQ_FG_STAMP") : nullptr;   // diagnostic builds
@@ -2536,7 +2582,8 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
       HIPCHK(hipMemsetAsync(stamp_d, 0, 1 << 20, s));
     }
     g.stamp = stamp_d;
-    HIPCHK(launch_fgemm(Xb, ix->iso_Mb, g, ix->cus, s));
+    if (g.i8) HIPCHK(launch_fgemm(Xq, ix->iso_Mq, g, ix->cus, s));
+    else HIPCHK(launch_fgemm(Xb, ix->iso_Mb, g, ix->cus, s));
     if (stamp_f) {
       std::vector<unsigned long long> hs(1 << 17);
       HIPCHK(hipMemcpyAsync(hs.data(), stamp_d, 1 << 20, hipMemcpyDeviceToHost, s));
@@ -2575,6 +2622,7 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
                     hipStream_t s, bool allow_filter) {
   const bool general = k > 64;
   const bool filt = !general && allow_filter && use_filter(ix, k);
+  if (allow_filter) ix->n_fg_i8 = 0;
   if (!general && allow_filter && use_filter(ix, k, kStreamMinRows) && use_stream(ix, nq, k))
     return stream_topk_impl(ix, q, nq, k, ids, scores, s);
   const int kl = k <= 16 ? 16 : 64;
@@ -2718,7 +2766,7 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
   if (allow_filter) {
     ix->stats[0] = filt ? nq : 0;
     ix->stats[1] = n_fallback;
-    ix->stats[2] = filt ? 1 : 0;
+    ix->stats[2] = filt ? 1 + ((int64_t)std::min(ix->n_fg_i8, 32767) << 16) : 0;   // (<< 16: its int8 launches)
     ix->stats[3] = filt && nq > 0 ? (cand_sum + nq / 2) / nq : 0;
     ix->stats[4] = filt && nq > 0 ? (exact_sum + nq / 2) / nq : 0;
     ix->stats[5] = filt ? ix->n_samp : 0;

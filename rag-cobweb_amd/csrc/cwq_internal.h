@@ -426,6 +426,11 @@ struct FgArgs {
   int all_uniform;                        // every row tile of the launch is uniform (TileF)
   int raw;                                // all-uniform filter launch that appends raw records {q, row, d, ex}:
                                           // bucket_raw_kernel turns them into bounds (not the categorize tables)
+  int i8;                                 // raw launch on the int8 operands (fgemm_kernel<0, true, true, true>):
+                                          // Xb / Mb are int8 [..][DPB]; the bounds take qinfo8 / rf8 / tf8
+  const float4* qinfo8;                   // [nq_pad] {|x'|^2, |x_hi8|, |x_lo8|, s_x} (launch_query_prep_i8)
+  const RowF* rf8;                        // the rows' int8 constants (launch_rows_i8: R0 = s_r)
+  const TileF* tf8;                       // tf with the int8 tile maxima of beta and delta (launch_tiles_i8)
   int qgroups, rgroups;                  // XCD split (qgroups * rgroups == 8)
   int order;                              // tile order: 0 static q-fastest, 1 static r-fastest, 2 dynamic
   int* tctr;                              // order 2: per-XCD tile counters [8] (zeroed before the launch)
@@ -716,6 +721,9 @@ hipError_t launch_rows_i8(const float* Mf, int DP, int D, const float* c, int DP
 // queries likewise: Xq [nq16][DPB], qinfo8 {|x'|^2, |x_hi|, |x_lo|, s_x}
 hipError_t launch_query_prep_i8(const float* q, int64_t nq, int D, const float* c, int DPB, int64_t nq16, void* Xq,
                                 float4* qinfo8, hipStream_t s);
+// per row tile, for the batch filter's int8 launches: tf8[t] = tf[t] with beta_max / delta_max
+// taken over the tile's usable rows of rf8
+hipError_t launch_tiles_i8(const TileF* tf, const RowF* rf8, int n_rt, TileF* tf8, hipStream_t s);
 struct StreamArgs {
   int DPB, nq, nqb;            // queries, 16-query blocks (nqb * 16 >= nq)
   int64_t nrows;               // isotropic filter rows

@@ -24,6 +24,9 @@
 //      (<= tau_k), exact fp32 keys of the candidates with u >= T2, exact top-k.
 //   Queries whose lists overflow (or have no usable threshold) are flagged and re-run
 //   by the exact scan, so the result never depends on the filter's statistics.
+//   On flat trees that hold the int8 row panel the late filter launches run on int8
+//   operands (v_mfma_i32_16x16x64_i8, half the K steps; fgemm_kernel's I8 comment): the
+//   same pipeline with the int8 split's norms in the bounds.
 //
 // CDNA4 mapping of fgemm: persistent, one 512-thread workgroup per CU,
 // 256 queries x 256 rows per tile, 8 waves as 2 (queries) x 4 (rows), each 128 x 64 =
@@ -39,6 +42,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "cwq_internal.h"
 
@@ -47,6 +51,7 @@ namespace cwq {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) void glb_void;
 
@@ -192,6 +197,36 @@ hipError_t launch_rows_i8(const float* Mf, int DP, int D, const float* c, int DP
   if (DPB % 64) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rows_i8_kernel, dim3((unsigned)((ld + 3) / 4)), dim3(256), 0, s, Mf, DP, D, c, DPB, ld, rf,
                      (int8_t*)Mq, rf8);
+  return hipGetLastError();
+}
+
+// Row tiles of the int8 panel (launch_tiles_i8): one workgroup of kFgTile threads per tile.
+__global__ __launch_bounds__(kFgTile) void tiles_i8_kernel(const TileF* __restrict__ tf, const RowF* __restrict__ rf8,
+                                                           TileF* tf8) {
+  __shared__ float sb[kFgTile / kWave], sd[kFgTile / kWave];
+  const RowF f = rf8[(size_t)blockIdx.x * kFgTile + threadIdx.x];
+  float b = f.par >= -1 ? f.beta : 0.f, d = f.par >= -1 ? f.delta : 0.f;
+  for (int off = 32; off > 0; off >>= 1) {
+    b = fmaxf(b, __shfl_xor(b, off, 64));
+    d = fmaxf(d, __shfl_xor(d, off, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sb[threadIdx.x >> 6] = b;
+    sd[threadIdx.x >> 6] = d;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    TileF t = tf[blockIdx.x];
+    t.beta_max = fmaxf(fmaxf(sb[0], sb[1]), fmaxf(sb[2], sb[3]));
+    t.delta_max = fmaxf(fmaxf(sd[0], sd[1]), fmaxf(sd[2], sd[3]));
+    tf8[blockIdx.x] = t;
+  }
+}
+
+hipError_t launch_tiles_i8(const TileF* tf, const RowF* rf8, int n_rt, TileF* tf8, hipStream_t s) {
+  static_assert(kFgTile == 4 * kWave, "tiles_i8_kernel reduces four waves");
+  if (n_rt <= 0) return hipSuccess;
+  hipLaunchKernelGGL(tiles_i8_kernel, dim3((unsigned)n_rt), dim3(kFgTile), 0, s, tf, rf8, tf8);
   return hipGetLastError();
 }
 
@@ -713,10 +748,13 @@ __device__ __forceinline__ int fg_swz(int r) { return (4 - ((r >> 2) & 3)) & 3; 
 // per-lane 32-bit byte offset fixed for the kernel (row within the 16-row piece, swizzled
 // chunk), so issuing a piece costs no 64-bit VALU math; the LDS destination (M0) is
 // computed on the scalar unit from the wave-uniform wave index.
+// ES: operand bytes per dim (2: bf16, k0 in steps of 32; 1: int8, steps of 64 -- the same
+// 64 B per row and stage).
+template <int ES = 2>
 __device__ __forceinline__ void fg_stage(const __bf16* __restrict__ Xb, const __bf16* __restrict__ Mb, int DPB, int q0,
                                          int r0, int k0, char* sb, int wave, const uint32_t* loff, int ipart = -1) {
-  const char* gA = reinterpret_cast<const char*>(Xb) + ((size_t)q0 * DPB + k0) * 2;
-  const char* gB = reinterpret_cast<const char*>(Mb) + ((size_t)r0 * DPB + k0) * 2;
+  const char* gA = reinterpret_cast<const char*>(Xb) + ((size_t)q0 * DPB + k0) * ES;
+  const char* gB = reinterpret_cast<const char*>(Mb) + ((size_t)r0 * DPB + k0) * ES;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     if (ipart >= 0 && i != ipart) continue;
@@ -742,10 +780,12 @@ __device__ __forceinline__ TileF fg_tile_const(const TileF* p, int i) {
 // Raw record {q, row, d, ex} of an all-uniform launch -> its rigorous bounds, from the same
 // inputs and with the same fg_bounds2 as the in-kernel path: qinfo[q], rf[row], the row
 // tile's parent prefix x invL (as the tile setup forms it).  True when the record is a
-// candidate: u >= T[q], the threshold the launch runs with.
+// candidate: u >= T[q], the threshold the launch runs with.  I8: a record of an int8
+// launch (d = s_x s_r acc, ex = 2^-21 |d|): the int8 split norms, qinfo8[q] and rf8[row].
+template <bool I8 = false>
 __device__ __forceinline__ bool fg_raw_bounds(const FgArgs& a, int q, int row, float d, float ex, float& u,
                                               float& lo) {
-  const RowF f = a.rf[row];
+  const RowF f = (I8 ? a.rf8 : a.rf)[row];
   if (f.par < -1) return false;
   const TileF tf = a.tf[row / kFgTile];
   float Pq = 0.f, Pql = 0.f;
@@ -759,7 +799,7 @@ __device__ __forceinline__ bool fg_raw_bounds(const FgArgs& a, int q, int row, f
   }
   // (__fmul_rn: the rounded products the tile setup stores, never contracted into fg_bounds2's sums)
   const float pi = __fmul_rn(Pq, tf.invL), pl = __fmul_rn(Pql, tf.invL);
-  fg_bounds2(d, ex, a.qinfo[q], f, pi, pl, a.eps_n, a.slack, u, lo);
+  fg_bounds2(d, ex, (I8 ? a.qinfo8 : a.qinfo)[q], f, pi, pl, a.eps_n, a.slack, u, lo);
   return u >= a.T[(size_t)q * a.ldT];
 }
 
@@ -771,10 +811,44 @@ __device__ __forceinline__ bool fg_raw_bounds(const FgArgs& a, int q, int row, f
 // records {q, row, d, ex} straight from the accumulators and bucket_raw_kernel evaluates
 // fg_bounds2 and u >= T; the record list is carried from tile to tile and the setup
 // barrier is the tile's only workgroup barrier outside the K loop (see "RAW ordering").
-template <int MODE, bool ALLUNI, bool RAW = false>
+// I8 (with RAW): int8 operands (launch_query_prep_i8 / launch_rows_i8; Xb and Mb point at
+// int8 [..][DPB]) and v_mfma_i32_16x16x64_i8.  A stage is 64 dims deep -- the same 64 B per
+// row, so the stage images, swizzle, ring, ping-pong and vmcnt counts are the bf16 ones --
+// and a tile has DPB / 64 of them, half the K steps and half the operand bytes.  Both
+// operands reach the MFMA through the same byte -> (lane, element) map, so the instruction's
+// k order inside a fragment does not matter.  The int32 accumulators start at 0 and hold
+// the exact integer dot; the epilogue replaces each by t = fl(float(acc) s_r) and tests
+//   fmaf(t, s_x, R_r) - Qv_q >= 0
+// with R_r the bf16 launch's row term (iso_rf: it holds no split norm) and Qv_q its query
+// term formed from the int8 norms: qinfo8 and tf8's tile maxima of beta and delta.  (The
+// integer-init form needs power-of-two scales common to a tile; the panel's are per row.)
+// Why the pretest is conservative for the bucket pass's u >= T[q].  That pass evaluates
+// fg_bounds2(d, ex) with the record's d = fl(t s_x), ex = 2^-21 |d|, and u >= T
+// rearranges (divide by g = 2 |hs| > 0, as for bf16) to
+//   d + ex + R*_r - Qv*_q >= 0,
+// R*, Qv* the bf16 derivation's row and query terms before their 4 gamma margins, Qv* with
+// the row's own beta, delta <= the tile maxima.  D = s_x s_r acc is exact in the reals; d
+// carries three fp32 roundings (int32 -> fp32, two multiplications) and the product t s_x
+// inside the fmaf two, so both are within 2^-22 |D| of D and the pretest's dot part is
+// >= d - 2^-21 |D|.  With ex that leaves 2^-20 |D| (1 + 2^-21) to cover, on top of the fp32
+// evaluation that the margins cover for bf16 -- here the fmaf's one rounding, 2^-24 (|D| +
+// |R_r|), and an exact-sign subtraction, against 4 gamma |R_r| in R_r's margin.  |D| = |x_hi.mu_hi| <= |x_hi| |mu_hi| and the
+// split gives |hi_d| <= 2 |v_d| per component (|v_d - hi_d| <= s / 2 <= |v_d| whenever
+// hi_d != 0), so |D| <= 4 |x'| |mu'| <= 2 (|x'|^2 + |mu'|^2) and 2^-20 |D| <= 2^-19 (qx +
+// rn2).  The margins hold 4 gamma (qx + rn2) with gamma = (DPB + 64) 2^-23 >= 1.5 * 2^-16:
+// 48 times that, and the int8 bound spends none of gamma on accumulation (the integer
+// sums are exact; rf8's beta has no gamma term).
+template <int MODE, bool ALLUNI, bool RAW = false, bool I8 = false>
 __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ Xb, const __bf16* __restrict__ Mb,
                                                     const FgArgs a) {
-  __shared__ __attribute__((aligned(16))) char smem[FLDS];
+  static_assert(!I8 || RAW, "int8 operands: raw-record launches only");
+  typedef typename std::conditional<I8, i32x4, bf16x8>::type frag_t;
+  typedef typename std::conditional<I8, i32x4, f32x4>::type acc_t;
+  constexpr int ES = I8 ? 1 : 2;   // operand bytes per dim
+  constexpr int SK = 64 / ES;      // dims per stage
+  // (I8: + float2 [2][FT], the tile's row terms {R_r, s_r} by tile parity -- the epilogue reads
+  // them there, and no row term stays in registers over the K loop)
+  __shared__ __attribute__((aligned(16))) char smem[FLDS + (I8 ? 2 * FT * 8 : 0)];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -785,7 +859,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
   const int ntl = fg_count(a, xcd);
   const bool dyn = a.order == 2;   // tiles claimed from a per-XCD counter (contiguous in-flight window)
   if (!dyn && lw >= ntl) return;
-  const int nk = a.DPB / FK;
+  const int nk = a.DPB / SK;
   float* s_qv = reinterpret_cast<float*>(smem + OFF_QV);
   float4* s_qi = reinterpret_cast<float4*>(smem + OFF_QI);
   float* s_pi = reinterpret_cast<float*>(smem + OFF_PI);
@@ -848,7 +922,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int row = wave * 32 + i * 16 + (lane >> 2);
-    loff[i] = (uint32_t)((row * a.DPB + (((lane & 3) ^ fg_swz(row)) * 8)) * 2);
+    loff[i] = (uint32_t)((row * a.DPB + (((lane & 3) ^ fg_swz(row)) * (16 / ES))) * ES);
   }
   // fragment read offsets (bytes) within an operand image; the swizzle term is the
   // same for every 32-row block, so one per-lane value per k-substep
@@ -875,7 +949,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
       if (ic_i < ntl) fg_decode(a, xcd, ic_i, ic_qt, ic_rt);
     }
     if (ic_i >= ntl) return;
-    if (!(a.dbg & 1)) fg_stage(Xb, Mb, a.DPB, ic_qt * FT, ic_rt * FT, ic_k * FK, smem + (issued & (FNBUF - 1)) * FSTAGE, wave, loff);
+    if (!(a.dbg & 1)) fg_stage<ES>(Xb, Mb, a.DPB, ic_qt * FT, ic_rt * FT, ic_k * SK, smem + (issued & (FNBUF - 1)) * FSTAGE, wave, loff);
     ++issued;
     if (++ic_k == nk) {
       ic_k = 0;
@@ -884,7 +958,10 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
   };
   issue_next();
   issue_next();
-  issue_next();
+  // (int8, DPB = 128: a tile has two stages, and a third one ahead would belong to the tile
+  // after the next, which no setup has claimed yet -- two in flight there; the waits below
+  // count what was issued)
+  if (!I8 || nk >= 3) issue_next();
   int qt, rt;
   int tile_no = 0;   // tiles done by this workgroup (diagnostics)
   (void)tile_no;
@@ -897,7 +974,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     s_cnt[2] = 0;    // its fill
   }
   if (RAW && lane == 0) s_cnt[16 + wave] = 0;   // (read and written by this wave only)
-  f32x4 acc[8][4];
+  acc_t acc[8][4];
 #if FG_STAMP
   // diagnostic: per-tile timestamps of wave 0 of workgroups 0..63, tiles 0..15: [wg][tile][8]
   // (0 setup start, 1 setup barrier passed, 2 K loop done, 3 fast-path test done, 4 slow
@@ -917,7 +994,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     const int q0 = qt * FT, r0 = rt * FT;
     // ---- tile setup: per-query terms in LDS, per-row terms in registers ----
     TileF tf;
-    if (MODE == 0) tf = fg_tile_const(a.tf, rt);
+    if (MODE == 0) tf = fg_tile_const(I8 ? a.tf8 : a.tf, rt);
     else tf.uniform = 0;
     const bool uni = ALLUNI || tf.uniform != 0;
     const bool multi = !ALLUNI && tf.uniform == 2;   // per-row parent prefix for survivors
@@ -932,8 +1009,10 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     const int qs = q0 + tid;
     float4 qi = make_float4(0.f, 0.f, 0.f, 0.f);
     float Tq = CWQ_INF, Pq = 0.f, Pql = 0.f;
+    float2 rw8 = make_float2(-CWQ_INF, 0.f);
+    (void)rw8;
     if (tid < FT) {
-      qi = a.qinfo[qs];
+      qi = (I8 ? a.qinfo8 : a.qinfo)[qs];
       if (qs < a.nq && MODE == 0) Tq = a.T[(size_t)qs * a.ldT];
       if (uni && tf.par >= 0 && qs < a.nq) {
         if (a.pb.dot) {
@@ -943,10 +1022,14 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
           Pql = a.P[pidx(a.ldP, a.pT, qs, tf.par)];
         }
       }
+      // I8: row r0 + tid's terms {R_r, s_r}, for LDS (s_r = 0 on unusable rows, whose R is -inf)
+      if (I8 && r0 + tid < a.nrows) rw8 = make_float2(a.rf[r0 + tid].R0, a.rf8[r0 + tid].R0);
     }
-    float R0[4];
+    float R0[4], SR[4];
+    (void)SR;
 #pragma unroll
     for (int jb = 0; jb < 4; ++jb) {
+      if (I8) break;   // (read from LDS in the epilogue)
       const int r = r0 + wr * 64 + jb * 16 + r16;
       // RAW: rows past the end can never pass the pretest (the epilogue tests nothing else)
       R0[jb] = (uni && r < a.nrows) ? a.rf[r].R0 : RAW ? -CWQ_INF : 0.f;
@@ -956,6 +1039,12 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     float* const s_qvt = RAW && (tile_no & 1) ? reinterpret_cast<float*>(smem + OFF_QI) : s_qv;
     if (tid < FT) {
       const float T = Tq;
+      // I8: the query scales s_x, by tile parity like the pretest terms, in the s_pi / s_pl
+      // regions (RAW tiles do not use them)
+      if constexpr (I8) {
+        (tile_no & 1 ? s_pl : s_pi)[tid] = qi.w;
+        reinterpret_cast<float2*>(smem + FLDS)[(tile_no & 1) * FT + tid] = rw8;
+      }
       qi.w = T;
       if (!RAW) s_qi[tid] = qi;
       // pretest query term for a parent prefix pi (smaller = more permissive)
@@ -1003,12 +1092,13 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     if (FG_LEAN && !RAW && MODE == 0 && tid == 0 && tile_no > 0) s_cnt[(tile_no & 1) ? 0 : 9] = 0;
     // RAW ordering.  S(n) is the setup barrier above of this workgroup's n-th tile, E(n)
     // its epilogue; a wave goes from E(n) straight into the setup of tile n+1.  Every
-    // s_barrier is workgroup-wide and the K loop holds at least 8 of them, so a wave is in
+    // s_barrier is workgroup-wide and the K loop holds at least 8 of them (int8: 4), so a wave is in
     // E(n) only after all waves passed S(n) and left everything before the K loop, and all
     // waves reach S(n+1) only after their own E(n).
     //  s_qv[parity]: written by setup n (before S(n)), read by the accumulator init and
     //    E(n) (after S(n): RAW ok).  Its next writer is setup n+2, after S(n+1), which
     //    every wave reaches after its E(n) (WAR ok); setup n+1 writes the other buffer.
+    //    (I8: the query scales in s_pi / s_pl and the row terms behind FLDS likewise.)
     //  s_cnt[8] (next tile claim): written by thread 0 in setup n, read by all right after
     //    S(n); rewritten in setup n+1, which wave 0 reaches through K loop n (WAR ok).
     //  s_cnt[0], s_rec (carried record list): appended to by E(n) with LDS atomics.  The
@@ -1027,20 +1117,27 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     }
     // ---- accumulator init: R_r - Qv_q on uniform tiles, 0 otherwise ----
     // 16x16x32 layout: acc[ib][jb][j] = C[query wq*128 + ib*16 + 4*c16 + j][row wr*64 + jb*16 + r16]
+    // (I8: 0 -- the integer accumulator holds the exact dot; the pretest terms join it in the epilogue)
 #pragma unroll
     for (int ib = 0; ib < 8; ++ib) {
-      const float4 qv4 = uni ? *reinterpret_cast<const float4*>(s_qvt + wq * 128 + ib * 16 + 4 * c16)
-                             : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (I8) {
 #pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        acc[ib][jb][0] = R0[jb] - qv4.x;
-        acc[ib][jb][1] = R0[jb] - qv4.y;
-        acc[ib][jb][2] = R0[jb] - qv4.z;
-        acc[ib][jb][3] = R0[jb] - qv4.w;
+        for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = acc_t{0, 0, 0, 0};
+      } else {
+        const float4 qv4 = uni ? *reinterpret_cast<const float4*>(s_qvt + wq * 128 + ib * 16 + 4 * c16)
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+          acc[ib][jb][0] = R0[jb] - qv4.x;
+          acc[ib][jb][1] = R0[jb] - qv4.y;
+          acc[ib][jb][2] = R0[jb] - qv4.z;
+          acc[ib][jb][3] = R0[jb] - qv4.w;
+        }
       }
     }
-    // ---- K loop: one 32-deep v_mfma_f32_16x16x32_bf16 substep per stage ----
-    bf16x8 xa1[8], xb0[4];
+    // ---- K loop: one 32-deep v_mfma_f32_16x16x32_bf16 (I8: 64-deep v_mfma_i32_16x16x64_i8)
+    // substep per stage ----
+    frag_t xa1[8], xb0[4];
     // Ping-pong: waves 0-3 and 4-7 (one of each per SIMD) run one barrier interval apart,
     // so in every interval one wave per SIMD issues its 32-MFMA cluster while its partner
     // works through its memory section:
@@ -1083,9 +1180,9 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
         const char* sA = sb + wq * 128 * 64 + foff16;
         const char* sB = sb + FT * 64 + wr * 64 * 64 + foff16;
 #pragma unroll
-        for (int ib = 0; ib < 8; ++ib) xa1[ib] = *reinterpret_cast<const bf16x8*>(sA + ib * 1024);
+        for (int ib = 0; ib < 8; ++ib) xa1[ib] = *reinterpret_cast<const frag_t*>(sA + ib * 1024);
 #pragma unroll
-        for (int jb = 0; jb < 4; ++jb) xb0[jb] = *reinterpret_cast<const bf16x8*>(sB + jb * 1024);
+        for (int jb = 0; jb < 4; ++jb) xb0[jb] = *reinterpret_cast<const frag_t*>(sB + jb * 1024);
       }
       ++gs;
       const int n_out = issued - gs - 1;
@@ -1099,8 +1196,10 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
 #pragma unroll
       for (int ib = 0; ib < 8; ++ib)
 #pragma unroll
-        for (int jb = 0; jb < 4; ++jb)
-          acc[ib][jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa1[ib], xb0[jb], acc[ib][jb], 0, 0, 0);
+        for (int jb = 0; jb < 4; ++jb) {
+          if constexpr (I8) acc[ib][jb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xa1[ib], xb0[jb], acc[ib][jb], 0, 0, 0);
+          else acc[ib][jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa1[ib], xb0[jb], acc[ib][jb], 0, 0, 0);
+        }
       FG_ST(3);
       if (t + 1 < nk || grp == 0) sbar();
       FG_ST(4);
@@ -1245,18 +1344,65 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     }
     if (MODE == 0 && uni) {
       bool any = false;
+      // I8: the tile's query scales, and the pretest of one element (kernel comment)
+      const float* const s_sx = (tile_no & 1) ? s_pl : s_pi;
+      // (t: the element's fl(float(acc) s_r), below; >= 0 passes)
+      auto pre8 = [](float t, float sx, float R, float qv) { return fmaf(t, sx, R) - qv; };
+      if constexpr (I8) {
 #pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          float m = -CWQ_INF;
-#pragma unroll
-          for (int ib = hf * 4; ib < hf * 4 + 4; ++ib)
-            m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fmaxf(acc[ib][jb][0], acc[ib][jb][1]),
-                                                   __builtin_fmaxf(acc[ib][jb][2], acc[ib][jb][3])));
-          anyb[jb][hf] = __ballot(m >= 0.f) != 0;
-          any = any || anyb[jb][hf];
+        for (int jb = 0; jb < 4; ++jb) {
+          const float2 rw = reinterpret_cast<const float2*>(smem + FLDS)[(tile_no & 1) * FT + wr * 64 + jb * 16 + r16];
+          R0[jb] = rw.x;
+          SR[jb] = rw.y;
         }
+        // the integer dots become t = fl(float(acc) s_r) in place: the pretest and the records
+        // read t, and one copy of the tile stays live (common subexpressions of the two kept
+        // a second one in registers, which spilled)
+#pragma unroll
+        for (int ib = 0; ib < 8; ++ib)
+#pragma unroll
+          for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              acc[ib][jb][j] = __float_as_int(__fmul_rn((float)acc[ib][jb][j], SR[jb]));
+        float m[4][2];
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) m[jb][0] = m[jb][1] = -CWQ_INF;
+#pragma unroll
+        for (int ib = 0; ib < 8; ++ib) {
+          const int ql = wq * 128 + ib * 16 + 4 * c16;
+          const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
+          const float4 sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
+#pragma unroll
+          for (int jb = 0; jb < 4; ++jb)
+            m[jb][ib >> 2] = __builtin_fmaxf(
+                m[jb][ib >> 2],
+                __builtin_fmaxf(__builtin_fmaxf(pre8(__int_as_float(acc[ib][jb][0]), sx4.x, R0[jb], qv4.x),
+                                                pre8(__int_as_float(acc[ib][jb][1]), sx4.y, R0[jb], qv4.y)),
+                                __builtin_fmaxf(pre8(__int_as_float(acc[ib][jb][2]), sx4.z, R0[jb], qv4.z),
+                                                pre8(__int_as_float(acc[ib][jb][3]), sx4.w, R0[jb], qv4.w))));
+        }
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+          for (int hf = 0; hf < 2; ++hf) {
+            anyb[jb][hf] = __ballot(m[jb][hf] >= 0.f) != 0;
+            any = any || anyb[jb][hf];
+          }
+      } else {
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+          for (int hf = 0; hf < 2; ++hf) {
+            float m = -CWQ_INF;
+#pragma unroll
+            for (int ib = hf * 4; ib < hf * 4 + 4; ++ib)
+              m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fmaxf(acc[ib][jb][0], acc[ib][jb][1]),
+                                                     __builtin_fmaxf(acc[ib][jb][2], acc[ib][jb][3])));
+            anyb[jb][hf] = __ballot(m >= 0.f) != 0;
+            any = any || anyb[jb][hf];
+          }
+      }
       FG_TS(3);
       if (!any) goto flush;
       if (RAW) {
@@ -1280,13 +1426,24 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
             const int ql = wq * 128 + ib * 16 + 4 * c16;
             const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
             const float qvj[4] = {qv4.x, qv4.y, qv4.z, qv4.w};
+            float4 sx4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (I8) sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
+            const float sxj[4] = {sx4.x, sx4.y, sx4.z, sx4.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              const float d0 = acc[ib][jb][j];
-              if (d0 >= 0.f) {
-                const float init = R0[jb] - qvj[j];
-                const float d = d0 - init;
-                const float ex = a.gamma * fabsf(init) + 0x1p-23f * (fabsf(d0) + fabsf(init));
+              float d0 = I8 ? __int_as_float(acc[ib][jb][j]) : (float)acc[ib][jb][j];
+              // (I8: t, opaque here so that nothing of the pretest above is kept for this block)
+              if (I8) asm volatile("" : "+v"(d0));
+              if (I8 ? pre8(d0, sxj[j], R0[jb], qvj[j]) >= 0.f : d0 >= 0.f) {
+                float d, ex;
+                if (I8) {
+                  d = __fmul_rn(d0, sxj[j]);
+                  ex = 0x1p-21f * fabsf(d);
+                } else {
+                  const float init = R0[jb] - qvj[j];
+                  d = d0 - init;
+                  ex = a.gamma * fabsf(init) + 0x1p-23f * (fabsf(d0) + fabsf(init));
+                }
                 const int4 rv = make_int4(q0 + ql + j, r, __float_as_int(d), __float_as_int(ex));
                 const int slot = atomicAdd(&s_cnt[0], 1);
                 if (slot < kFgCap) {
@@ -1309,7 +1466,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
               for (int k = lane; k < no; k += 64) {
                 const int4 rv = wrec[k];
                 float u, lo;
-                if (fg_raw_bounds(a, rv.x, rv.y, __int_as_float(rv.z), __int_as_float(rv.w), u, lo)) {
+                if (fg_raw_bounds<I8>(a, rv.x, rv.y, __int_as_float(rv.z), __int_as_float(rv.w), u, lo)) {
                   const int gs = atomicAdd(&a.gctr[1], 1);
                   if (gs < a.dir_cap) a.rec_dir[gs] = rv;
                   else a.qover[rv.x] = 1;
@@ -1512,8 +1669,11 @@ hipError_t launch_fgemm(const void* Xb, const void* Mb, const FgArgs& a, int n_w
   else if (a.mode == 2)
     hipLaunchKernelGGL((fgemm_kernel<2, false>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
                        (const __bf16*)Mb, a);
-  else if (a.raw && !a.all_uniform)
+  else if ((a.raw && !a.all_uniform) || (a.i8 && (!a.raw || a.DPB % 64 || !a.qinfo8 || !a.rf8 || !a.tf8)))
     return hipErrorInvalidValue;
+  else if (a.i8)   // Xb / Mb: the int8 operands
+    hipLaunchKernelGGL((fgemm_kernel<0, true, true, true>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
+                       (const __bf16*)Mb, a);
   else if (a.raw)
     hipLaunchKernelGGL((fgemm_kernel<0, true, true>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
                        (const __bf16*)Mb, a);
@@ -1562,12 +1722,14 @@ __global__ __launch_bounds__(256) void bucket_kernel(const int4* __restrict__ re
 // Raw records {q, row, d, ex} of an all-uniform launch (fgemm_kernel<0, true, true>): the
 // rigorous bounds are evaluated here (fg_raw_bounds) and the record is kept when u >= T[q],
 // the threshold the launch ran with (this pass runs before tighten_kernel raises it).
+// a.i8: the records of an int8 launch, bounded with the int8 split norms.
 __device__ __forceinline__ void bucket_raw_one(const FgArgs& a, const int4 r, int capq, int* qcnt, int* crow,
                                                float* cu, float* cl) {
   const int q = r.x, row = r.y;
   if ((unsigned)q >= (unsigned)a.nq || (unsigned)row >= (unsigned)a.nrows) return;
   float u, lo;
-  if (fg_raw_bounds(a, q, row, __int_as_float(r.z), __int_as_float(r.w), u, lo))
+  const float d = __int_as_float(r.z), ex = __int_as_float(r.w);
+  if (a.i8 ? fg_raw_bounds<true>(a, q, row, d, ex, u, lo) : fg_raw_bounds<false>(a, q, row, d, ex, u, lo))
     bucket_one(make_int4(q, row, __float_as_int(u), __float_as_int(lo)), capq, qcnt, a.qover, crow, cu, cl);
 }
 

@@ -184,6 +184,8 @@ class CobwebIndex:
         return {"filter_queries": int(out[0]), "fallback_queries": int(out[1]), "filter_used": bool(out[2]),
                 "path": {0: "scan", 1: "fgemm", 2: "stream"}.get(int(out[2]) & 255, "?"),
                 "int8_pass": bool(int(out[2]) & 256),
+                "fg_i8_launches": int(out[2]) >> 16,   # batch filter launches on the int8 operands
+
                 "candidates": int(out[3]), "exact_reranks": int(out[4]), "sample_rows": int(out[5])}
 
     def last_prune_stats(self):

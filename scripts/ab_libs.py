@@ -103,10 +103,13 @@ def main():
         print(f"round {r}: " + "  ".join(f"{os.path.basename(p)[:60]} {call[p][-1]:.2f}/{fg[p][-1]:.3f}" for p in paths),
               flush=True)
     base = statistics.median(fg[paths[0]])
-    for p in paths:
+    for p, ix in zip(paths, arms):
         mc, mf = statistics.median(call[p]), statistics.median(fg[p])
+        st = ix.last_stats()   # of the arm's last call
         print(f"{os.path.basename(p)[:60]}: call {mc:.3f} ms ({args.queries / mc * 1e3:.0f} q/s)  fgemm {mf:.3f} ms "
-              f"(x{base / mf:.3f} vs first)  min {min(fg[p]):.3f}", flush=True)
+              f"(x{base / mf:.3f} vs first)  min {min(fg[p]):.3f}  cand/q {st['candidates']} reranks/q "
+              f"{st['exact_reranks']} fallback {st['fallback_queries']} int8 launches {st.get('fg_i8_launches', 0)}",
+              flush=True)
 
 
 if __name__ == "__main__":

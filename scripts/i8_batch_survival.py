@@ -13,7 +13,10 @@ that the survivors per query estimate the full 1M-row case.  Reported: survivors
 query (x 1M / rows) and the fraction of 16-query x 64-row MFMA blocks holding a survivor
 (the blocks whose epilogue leaves the one-max-per-element fast path).
 
-    python scripts/i8_batch_survival.py [--rows 262144] [--queries 256]
+    python scripts/i8_batch_survival.py [--rows 262144] [--queries 256] [--hybrid]
+
+--hybrid adds the table of the policy the batch filter runs (bf16 launches up to a cut of
+the rows, int8 after it; hybrid() below) -- profiles/fgi8_model_c3.log, DESIGN Appendix C.1.
 """
 import argparse
 
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--full", type=int, default=1_000_000)
+    ap.add_argument("--hybrid", action="store_true", help="also the bf16-then-int8 policy table (hybrid())")
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     N, Q, D = args.rows, args.queries, args.dim
@@ -82,6 +86,65 @@ def main():
               f"{out[name][3]:.3f} (S units)", flush=True)
     print(f"int8 / bf16: survivors x{out['int8'][1] / out['bf16'][1]:.2f}, active blocks "
           f"x{out['int8'][2] / out['bf16'][2]:.2f}", flush=True)
+    if args.hybrid:
+        hybrid(args, S, dots, Xc, qs, gamma, K)
+
+
+def hybrid(args, S, dots, Xc, qs, gamma, K):
+    """The hybrid policy of run_iso_filter: bf16 launches over the first `cut` of
+    the rows set T (the K-th best bf16 upper bound there, frozen -- the pipeline tightens
+    again at 1/2, so this is pessimistic), int8 launches take the rest.  Per cut, for the rest
+    of the rows in bf16 and in int8: candidates per query (scaled to --full rows), raw records
+    per query (the pretest, with the 256-row tile maxima of beta and delta) and the share of
+    16x64 blocks holding a raw record; then the exact reranks per query when every candidate
+    keeps the bounds of the pass that produced it (T2 = K-th best upper bound of all
+    candidates; reranked: lower bound within T2)."""
+    N, Q = S.shape[1], S.shape[0]
+    scale = args.full / N
+
+    def widths(split, extra):
+        rh, rl = split(Xc.astype(np.float64))
+        xh, xl = split(qs.astype(np.float64))
+        nh, nl = np.linalg.norm(rh, axis=1), np.linalg.norm(rl, axis=1)
+        beta = nl + (gamma * nh if extra is None else 0.0)
+        delta = nh + nl
+        a, c = np.linalg.norm(xh, axis=1)[:, None], np.linalg.norm(xl, axis=1)[:, None]
+        w = 2 * (a * beta[None, :] + c * delta[None, :]) + (0.0 if extra is None else 2 * extra)
+        nt = N // 256 * 256
+        bm = np.repeat(beta[:nt].reshape(-1, 256).max(1), 256)
+        dm = np.repeat(delta[:nt].reshape(-1, 256).max(1), 256)
+        wt = np.full_like(w, np.inf)   # (rows of a last partial tile: always flagged)
+        wt[:, :nt] = 2 * (a * bm[None, :] + c * dm[None, :])
+        return w, np.maximum(w, wt)
+
+    wb, wbt = widths(lambda v: bf16_split(v.astype(np.float32)), None)
+    w8, w8t = widths(i8_split, 2.0 ** -21 * np.abs(dots))
+    print(f"hybrid policy, K = {K} of {N} rows, x{scale:.2f} to {args.full} rows; kFgCapQ / 4 = 1024")
+    print("| bf16 over the first | rest bf16: cand/q, blocks | rest int8: cand/q, raw records/q, blocks | total cand/q "
+          "bf16 / hybrid | reranks/q bf16 / hybrid |")
+    for num, den in ((1, 32), (3, 32), (1, 4), (1, 2)):
+        n0 = N * num // den
+        thr = np.partition((S + wb)[:, :n0], K - 1, axis=1)[:, K - 1][:, None]
+        head = ((S - wb)[:, :n0] <= thr)
+        rest = {"bf16": ((S - wb)[:, n0:] <= thr, (S - wbt)[:, n0:] <= thr),
+                "int8": ((S - w8)[:, n0:] <= thr, (S - w8t)[:, n0:] <= thr)}
+
+        def blocks(m):
+            nq_, nr_ = Q // 16, m.shape[1] // 64
+            return m[:nq_ * 16, :nr_ * 64].reshape(nq_, 16, nr_, 64).any(axis=(1, 3)).mean()
+
+        rer = {}
+        for name, wr in (("bf16", wb), ("int8", w8)):
+            cand = np.concatenate([head, rest[name][0]], axis=1)
+            ub = np.where(cand, np.concatenate([(S + wb)[:, :n0], (S + wr)[:, n0:]], axis=1), np.inf)
+            lo = np.concatenate([(S - wb)[:, :n0], (S - wr)[:, n0:]], axis=1)
+            t2 = np.partition(ub, K - 1, axis=1)[:, K - 1][:, None]
+            rer[name] = (cand & (lo <= t2)).sum(1).mean() * scale
+        cb, c8 = rest["bf16"][0].sum(1).mean() * scale, rest["int8"][0].sum(1).mean() * scale
+        hd = head.sum(1).mean() * scale
+        print(f"| {num}/{den} | {cb:.0f}, {100 * blocks(rest['bf16'][1]):.0f} % | {c8:.0f}, "
+              f"{rest['int8'][1].sum(1).mean() * scale:.0f}, {100 * blocks(rest['int8'][1]):.0f} % | "
+              f"{hd + cb:.0f} / {hd + c8:.0f} | {rer['bf16']:.0f} / {rer['int8']:.0f} |", flush=True)
 
 
 if __name__ == "__main__":
