@@ -52,6 +52,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) void glb_void;
 
@@ -1348,47 +1349,69 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
       const float* const s_sx = (tile_no & 1) ? s_pl : s_pi;
       // (t: the element's fl(float(acc) s_r), below; >= 0 passes)
       auto pre8 = [](float t, float sx, float R, float qv) { return fmaf(t, sx, R) - qv; };
-      if constexpr (I8) {
+      // RAW: one flag per 16 x 16 sub-block (jb, ib) of the wave's tile, bit jb * 8 + ib: some
+      // lane holds a pretest survivor among its four elements there.  The pretest works on
+      // the adjacent element pairs (0, 1) and (2, 3) of an accumulator as float2, which
+      // selects the packed fp32 forms (v_pk_mul / v_pk_fma / v_pk_add: two IEEE operations
+      // per issue; the epilogue issues no MFMA beside them; gfx950 has no packed fp32 max,
+      // the four values of a sub-block reduce with v_max3 + v_max).  Every element still
+      // gets the scalar form's operations in its order, each rounded once, so the values
+      // are pre8's bit for bit (no contraction: pragma below).
+      uint32_t sbm = 0;
+      if constexpr (RAW) {
+#pragma clang fp contract(off)
+        if constexpr (I8) {
 #pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
-          const float2 rw = reinterpret_cast<const float2*>(smem + FLDS)[(tile_no & 1) * FT + wr * 64 + jb * 16 + r16];
-          R0[jb] = rw.x;
-          SR[jb] = rw.y;
+          for (int jb = 0; jb < 4; ++jb) {
+            const float2 rw = reinterpret_cast<const float2*>(smem + FLDS)[(tile_no & 1) * FT + wr * 64 + jb * 16 + r16];
+            R0[jb] = rw.x;
+            SR[jb] = rw.y;
+          }
+          // the integer dots become t = fl(float(acc) s_r) in place: the pretest and the records
+          // read t, and one copy of the tile stays live (common subexpressions of the two kept
+          // a second one in registers, which spilled)
+#pragma unroll
+          for (int ib = 0; ib < 8; ++ib)
+#pragma unroll
+            for (int jb = 0; jb < 4; ++jb) {
+              const f32x2 sr2 = {SR[jb], SR[jb]};
+#pragma unroll
+              for (int h = 0; h < 4; h += 2) {
+                const f32x2 t = f32x2{(float)acc[ib][jb][h], (float)acc[ib][jb][h + 1]} * sr2;
+                acc[ib][jb][h] = __float_as_int(t.x);
+                acc[ib][jb][h + 1] = __float_as_int(t.y);
+              }
+            }
         }
-        // the integer dots become t = fl(float(acc) s_r) in place: the pretest and the records
-        // read t, and one copy of the tile stays live (common subexpressions of the two kept
-        // a second one in registers, which spilled)
-#pragma unroll
-        for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-          for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              acc[ib][jb][j] = __float_as_int(__fmul_rn((float)acc[ib][jb][j], SR[jb]));
-        float m[4][2];
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) m[jb][0] = m[jb][1] = -CWQ_INF;
 #pragma unroll
         for (int ib = 0; ib < 8; ++ib) {
           const int ql = wq * 128 + ib * 16 + 4 * c16;
-          const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
-          const float4 sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
-#pragma unroll
-          for (int jb = 0; jb < 4; ++jb)
-            m[jb][ib >> 2] = __builtin_fmaxf(
-                m[jb][ib >> 2],
-                __builtin_fmaxf(__builtin_fmaxf(pre8(__int_as_float(acc[ib][jb][0]), sx4.x, R0[jb], qv4.x),
-                                                pre8(__int_as_float(acc[ib][jb][1]), sx4.y, R0[jb], qv4.y)),
-                                __builtin_fmaxf(pre8(__int_as_float(acc[ib][jb][2]), sx4.z, R0[jb], qv4.z),
-                                                pre8(__int_as_float(acc[ib][jb][3]), sx4.w, R0[jb], qv4.w))));
-        }
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-          for (int hf = 0; hf < 2; ++hf) {
-            anyb[jb][hf] = __ballot(m[jb][hf] >= 0.f) != 0;
-            any = any || anyb[jb][hf];
+          f32x2 qv2[2] = {}, sx2[2] = {};
+          if constexpr (I8) {
+            const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
+            const float4 sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
+            qv2[0] = f32x2{qv4.x, qv4.y};
+            qv2[1] = f32x2{qv4.z, qv4.w};
+            sx2[0] = f32x2{sx4.x, sx4.y};
+            sx2[1] = f32x2{sx4.z, sx4.w};
           }
+#pragma unroll
+          for (int jb = 0; jb < 4; ++jb) {
+            f32x2 p[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              if constexpr (I8) {
+                const f32x2 t = {__int_as_float(acc[ib][jb][2 * h]), __int_as_float(acc[ib][jb][2 * h + 1])};
+                p[h] = __builtin_elementwise_fma(t, sx2[h], f32x2{R0[jb], R0[jb]}) - qv2[h];
+              } else {
+                p[h] = f32x2{(float)acc[ib][jb][2 * h], (float)acc[ib][jb][2 * h + 1]};
+              }
+            }
+            const f32x2 m2 = __builtin_elementwise_max(p[0], p[1]);
+            if (__ballot(__builtin_fmaxf(m2.x, m2.y) >= 0.f) != 0) sbm |= 1u << (jb * 8 + ib);
+          }
+        }
+        any = sbm != 0;
       } else {
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb)
@@ -1415,68 +1438,83 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
         // just consumed (the other instantiations' wsc), free until a wave issues the next
         // tile's first K step -- after the next setup barrier, which this wave reaches
         // after this epilogue.
+        // The walk is one rolled loop over the set bits of the (wave-uniform) mask: a switch
+        // copies the sub-block's four accumulators and its row term out of the register
+        // tile, and one body -- four predicated appends, one overflow drain -- serves all 32
+        // positions (unrolled, the 32 bodies with their drains were 18k instructions).  Each
+        // append claims its slot with an LDS atomic, which the compiler aggregates per wave;
+        // one claim per sub-block from the four ballots measured the same (DESIGN C.1).
         int4* const wrec = reinterpret_cast<int4*>(wsc);
-        bool ovf = false;
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
-          const int r = r0 + wr * 64 + jb * 16 + r16;
-#pragma unroll
-          for (int ib = 0; ib < 8; ++ib) {
-            if (!anyb[jb][ib >> 2]) continue;
-            const int ql = wq * 128 + ib * 16 + 4 * c16;
-            const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
-            const float qvj[4] = {qv4.x, qv4.y, qv4.z, qv4.w};
-            float4 sx4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (I8) sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
-            const float sxj[4] = {sx4.x, sx4.y, sx4.z, sx4.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float d0 = I8 ? __int_as_float(acc[ib][jb][j]) : (float)acc[ib][jb][j];
-              // (I8: t, opaque here so that nothing of the pretest above is kept for this block)
-              if (I8) asm volatile("" : "+v"(d0));
-              if (I8 ? pre8(d0, sxj[j], R0[jb], qvj[j]) >= 0.f : d0 >= 0.f) {
-                float d, ex;
-                if (I8) {
-                  d = __fmul_rn(d0, sxj[j]);
-                  ex = 0x1p-21f * fabsf(d);
-                } else {
-                  const float init = R0[jb] - qvj[j];
-                  d = d0 - init;
-                  ex = a.gamma * fabsf(init) + 0x1p-23f * (fabsf(d0) + fabsf(init));
-                }
-                const int4 rv = make_int4(q0 + ql + j, r, __float_as_int(d), __float_as_int(ex));
-                const int slot = atomicAdd(&s_cnt[0], 1);
-                if (slot < kFgCap) {
-                  s_rec[slot] = rv;
-                } else {   // list full: to the wave's overflow area (4 values x 64 lanes fit)
-                  wrec[atomicAdd(&s_cnt[16 + wave], 1)] = rv;
-                  ovf = true;
-                }
-              }
-            }
-            if (__builtin_expect(__any(ovf), 0)) {
-              // Dense tiles, and data on which the pretest's margins pass far more than
-              // u >= T does: the rigorous test here (a rolled loop, global loads), so that
-              // the direct region takes candidates only, as on the in-kernel path.
-              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-              __builtin_amdgcn_wave_barrier();
-              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-              const int no = s_cnt[16 + wave];
+        uint32_t todo = sbm;
 #pragma unroll 1
-              for (int k = lane; k < no; k += 64) {
-                const int4 rv = wrec[k];
-                float u, lo;
-                if (fg_raw_bounds<I8>(a, rv.x, rv.y, __int_as_float(rv.z), __int_as_float(rv.w), u, lo)) {
-                  const int gs = atomicAdd(&a.gctr[1], 1);
-                  if (gs < a.dir_cap) a.rec_dir[gs] = rv;
-                  else a.qover[rv.x] = 1;
-                }
+        while (todo) {
+          const int sb = __builtin_ctz(todo);
+          todo &= todo - 1;
+          const int jb = sb >> 3, ib = sb & 7;
+          float d0j[4] = {0.f, 0.f, 0.f, 0.f}, Rv = 0.f;
+#define FG_SB(JB, IB)                                                                                   \
+  case (JB) * 8 + (IB):                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                       \
+        d0j[j] = I8 ? __int_as_float(acc[IB][JB][j]) : (float)acc[IB][JB][j];                           \
+    Rv = R0[JB];                                                                                        \
+    break;
+#define FG_SB8(JB) FG_SB(JB, 0) FG_SB(JB, 1) FG_SB(JB, 2) FG_SB(JB, 3) FG_SB(JB, 4) FG_SB(JB, 5) FG_SB(JB, 6) FG_SB(JB, 7)
+          switch (sb) {
+            FG_SB8(0) FG_SB8(1) FG_SB8(2) FG_SB8(3)
+          }
+#undef FG_SB8
+#undef FG_SB
+          const int r = r0 + wr * 64 + jb * 16 + r16;
+          const int ql = wq * 128 + ib * 16 + 4 * c16;
+          const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
+          const float qvj[4] = {qv4.x, qv4.y, qv4.z, qv4.w};
+          float4 sx4 = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (I8) sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
+          const float sxj[4] = {sx4.x, sx4.y, sx4.z, sx4.w};
+          bool ovf = false;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (I8 ? pre8(d0j[j], sxj[j], Rv, qvj[j]) >= 0.f : d0j[j] >= 0.f) {
+              const float d0 = d0j[j];
+              float d, ex;
+              if (I8) {
+                d = __fmul_rn(d0, sxj[j]);
+                ex = 0x1p-21f * fabsf(d);
+              } else {
+                const float init = Rv - qvj[j];
+                d = d0 - init;
+                ex = a.gamma * fabsf(init) + 0x1p-23f * (fabsf(d0) + fabsf(init));
               }
-              __builtin_amdgcn_wave_barrier();   // the area is read before it is refilled
-              if (lane == 0) s_cnt[16 + wave] = 0;
-              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-              ovf = false;
+              const int4 rv = make_int4(q0 + ql + j, r, __float_as_int(d), __float_as_int(ex));
+              const int slot = atomicAdd(&s_cnt[0], 1);
+              if (slot < kFgCap) {
+                s_rec[slot] = rv;
+              } else {   // list full: to the wave's overflow area (4 values x 64 lanes fit)
+                wrec[atomicAdd(&s_cnt[16 + wave], 1)] = rv;
+                ovf = true;
+              }
             }
+          if (__builtin_expect(__any(ovf), 0)) {
+            // Dense tiles, and data on which the pretest's margins pass far more than
+            // u >= T does: the rigorous test here (a rolled loop, global loads), so that
+            // the direct region takes candidates only, as on the in-kernel path.
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int no = s_cnt[16 + wave];
+#pragma unroll 1
+            for (int k = lane; k < no; k += 64) {
+              const int4 rv = wrec[k];
+              float u, lo;
+              if (fg_raw_bounds<I8>(a, rv.x, rv.y, __int_as_float(rv.z), __int_as_float(rv.w), u, lo)) {
+                const int gs = atomicAdd(&a.gctr[1], 1);
+                if (gs < a.dir_cap) a.rec_dir[gs] = rv;
+                else a.qover[rv.x] = 1;
+              }
+            }
+            __builtin_amdgcn_wave_barrier();   // the area is read before it is refilled
+            if (lane == 0) s_cnt[16 + wave] = 0;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           }
         }
         goto flush;
