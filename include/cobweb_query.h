@@ -110,8 +110,11 @@ int cwq_index_info(const cwq_index* idx, int64_t* out8);
  * index's bf16 filter operands): out[0] = 1 when isotropic rows are stored centred at
  * their group centre's mean (clustered trees, cwq_group.hip; CWQ_GROUP_CENTRE=0 / 1 at
  * index creation: off / on wherever it applies), out[1] = groups, out[2] = group-centred
- * rows, out[3] = 1 when the per-call int8 panel was built. */
-int cwq_index_filter_info(const cwq_index* idx, int64_t* out4);
+ * rows, out[3] = 1 when the per-call int8 panel was built, out[4] = the hub rows of the
+ * batch filter's threshold sample (the rows with the largest query-independent key term,
+ * appended to the strided sample; CWQ_FG_HUB_DIV = n at index creation: NL_iso / n rows,
+ * 0: none). */
+int cwq_index_filter_info(const cwq_index* idx, int64_t* out5);
 
 /* The tree-adaptive cut the index chose (no reference counterpart): out[0] =
  * groups (centre nodes; 0: none planned), out[1] = top nodes (the root and the centres'

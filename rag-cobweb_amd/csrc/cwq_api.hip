@@ -116,6 +116,11 @@ struct cwq_index {
   RowF* iso_rf8 = nullptr;
   TileF* iso_tf8 = nullptr;   // iso_tf with the int8 tile maxima (the batch filter's int8 launches)
   int i8_state = 0;
+  bool i8_by_size = false;   // the panel was built with the index by the size rule (ensure_i8), not by a knob
+  // the batch filter's early int8 schedule (fg_i8_from) went back to the quarter rule: a call
+  // on it passed too many candidates or re-ran a query (until cwq_set_filter)
+  bool i8_early_off = false;
+  bool i8_early_ran = false;   // the current call ran the early schedule
   std::vector<int> tile_uni_prefix;   // prefix counts of uniform row tiles (all_uniform per launch range)
   int n_multi_tiles = 0;              // tiles with several parents (TileF uniform 2)
   // the same tables for the categorize key min(BF[parent], lp) (cwq_categorize through the
@@ -125,6 +130,7 @@ struct cwq_index {
   std::vector<int> cat_uni_prefix;
   float cat_dconst = 0.f;
   int n_samp = 0, ld_s = 0;                    // sample rows, padded to 256
+  int n_hub = 0;                               // of n_samp: the hub rows (largest row terms R0)
   // group-centred filter rows (cwq_group.hip; clustered trees): the isotropic rows below a
   // depth-1 internal node g are centred at its mean grp_c[g]; grp_par[p] = the group of
   // internal node p's rows (-1: root-centred), grp_F[p] = hs / invL of p's rows (Fast),
@@ -629,6 +635,9 @@ int build_filter(cwq_index* ix, const float* mean, const int64_t* d_rows, const 
     const char* e = getenv("CWQ_FG_MAX_PARENTS");
     return e && *e ? std::max(1, atoi(e)) : kFgMaxTileParents;
   }();
+  // Fast key row terms R0 of the rows a uniform tile may hold (-inf: none), for the hub rows
+  // of the threshold sample below
+  std::vector<float> hub_key(NLi, -INFINITY);
   auto tables = [&](bool cat, std::vector<RowF>& rf, std::vector<TileF>& tf) {
     rf.assign(ld, RowF{});
     std::vector<double> gr(ld, 0.0);
@@ -662,6 +671,7 @@ int build_filter(cwq_index* ix, const float* mean, const int64_t* d_rows, const 
         double R = hl / g - 0.5 * rn2 + 0.5 * fc.eps_n * rn2 + fc.slack * (std::fabs(hl) / g + 1.5 * rn2);
         R += 4.0 * fc.gamma * (std::fabs(R) + std::fabs(hl) / g + rn2);
         f.R0 = round_up_f(R);
+        if (!cat && f.par >= -1 && std::isfinite(f.R0)) hub_key[r] = f.R0;
       } else {
         f.R0 = 0.f;   // only ever on non-uniform tiles
       }
@@ -760,6 +770,42 @@ int build_filter(cwq_index* ix, const float* mean, const int64_t* d_rows, const 
           srow.push_back(r);
         }
       }
+    }
+  }
+  // hub rows: the rows with the largest query-independent term R0 of the Fast key (small
+  // |mu'|^2) are the likely top-k of any query, so with them in the sample the first launch
+  // already runs near the threshold the call ends with (C3: the K-th best key of the
+  // lowest-norm 1/128 of the rows has median rank 25 of 1M, of a strided 1/128 rank ~1,100).
+  // H = S/2 rows by default (CWQ_FG_HUB_DIV = n: NL_iso/n; 0: none), appended after the
+  // strided rows -- S is a multiple of 256, so the sample pass's 4-row groups keep their
+  // members -- ties by smaller row index, rows of the strided sample skipped (T bounds the
+  // K-th best key over DISTINCT rows).  The sample pass keeps one maximum per 4 consecutive
+  // sample rows, so hub j of H goes to group j mod H/4: the best H/4 hubs each lead a group.
+  ix->n_hub = 0;
+  if (!ix->grp_mode && NLi >= 4 * S) {
+    const char* hd = getenv("CWQ_FG_HUB_DIV");
+    const int64_t want = hd && *hd ? (atoi(hd) > 0 ? NLi / atoi(hd) / kFgTile * kFgTile : 0) : S / 2;
+    const int H = (int)std::min<int64_t>(want, (32768 - (int64_t)srow.size()) / 4 * 4);
+    if (H > 0) {
+      std::vector<int> cand;
+      cand.reserve(NLi);
+      for (int r = 0; r < NLi; ++r)
+        if (hub_key[r] > -INFINITY) cand.push_back(r);
+      // the best H rows outside the strided sample are among the best H + |strided| rows
+      const size_t top = std::min(cand.size(), (size_t)H + srow.size());
+      std::partial_sort(cand.begin(), cand.begin() + top, cand.end(), [&](int a, int b) {
+        return hub_key[a] > hub_key[b] || (hub_key[a] == hub_key[b] && a < b);
+      });
+      std::vector<char> in(NLi, 0);
+      for (int r : srow) in[r] = 1;
+      std::vector<int> hub;
+      hub.reserve(H);
+      for (size_t i = 0; i < top && (int)hub.size() < H; ++i)
+        if (!in[cand[i]]) hub.push_back(cand[i]);
+      const int nh = (int)hub.size(), ng = (nh + 3) / 4;
+      for (int g = 0; g < ng; ++g)
+        for (int j = g; j < nh; j += ng) srow.push_back(hub[j]);
+      ix->n_hub = nh;
     }
   }
   const int ns = (int)srow.size();
@@ -978,6 +1024,7 @@ namespace {
 // the compact per-node form (VarSrc); both give the same index.
 bool use_int_bounds(const cwq_index* ix);
 bool ensure_i8(cwq_index* ix, hipStream_t s);
+bool i8_size_rule(const cwq_index* ix);
 
 int index_create_impl(int device, int64_t n_nodes, int32_t dim, const float* mean, const VarSrc& var,
                       const int64_t* parent, const int64_t* node_of_sentence, int64_t n_sent, const double* level_w,
@@ -1248,7 +1295,8 @@ int index_create_impl(int device, int64_t n_nodes, int32_t dim, const float* mea
   // the per-call path's int8 row panel is built here, with the index, when its policy
   // holds (flat trees, >= kI8MinBytes of int8 rows, room on the device): no allocation or
   // first-call latency inside a query
-  if (ix->NL_iso > 0 && !use_int_bounds(ix.get())) (void)ensure_i8(ix.get(), s);
+  if (ix->NL_iso > 0 && !use_int_bounds(ix.get()))
+    ix->i8_by_size = ensure_i8(ix.get(), s) && i8_size_rule(ix.get());
   HIPCHK(hipStreamSynchronize(s));
   *out = ix.release();
   return CWQ_OK;
@@ -1333,6 +1381,7 @@ extern "C" int cwq_index_filter_info(const cwq_index* idx, int64_t* o) {
   o[1] = idx->G;
   o[2] = idx->n_grp_rows;
   o[3] = idx->i8_state > 0 ? 1 : 0;
+  o[4] = idx->n_hub;
   return CWQ_OK;
 }
 
@@ -2082,10 +2131,11 @@ bool build_i8(cwq_index* ix, hipStream_t s) {
   ix->i8_state = 1;
   return true;
 }
+bool i8_size_rule(const cwq_index* ix) { return (int64_t)ix->NL_iso * ix->DPB >= kI8MinBytes; }
 bool ensure_i8(cwq_index* ix, hipStream_t s) {
   const char* e = getenv("CWQ_STREAM_I8");
   if ((e && *e && atoi(e) == 0) || ix->grp_mode) return false;
-  if (!(e && *e && atoi(e) == 1) && (int64_t)ix->NL_iso * ix->DPB < kI8MinBytes) return false;
+  if (!(e && *e && atoi(e) == 1) && !i8_size_rule(ix)) return false;
   return build_i8(ix, s);
 }
 
@@ -2093,7 +2143,16 @@ bool ensure_i8(cwq_index* ix, hipStream_t s) {
 // first filter phase that takes the int8 operands, nph for none.  By default the phases that
 // start at or past a quarter of the row tiles, on an index that has its int8 panel: the bf16
 // launches before them have raised T, so the wider int8 bounds pass few candidates
-// (profiles/fgi8_model_c3.log).  CWQ_FG_I8 (read per call; tests and in-process A/Bs):
+// (profiles/fgi8_model_c3.log).  The early schedule: an index that got its panel by the size
+// rule when it was built and whose sample holds hub rows (build_filter) runs every launch on
+// the int8 operands -- the hub rows put the sample threshold near the final one, so the first
+// launch passes what the late ones do (profiles/hub_model_c3.log).  Row terms that say nothing
+// about the keys (unit-norm rows around a zero mean) leave it at the strided sample's
+// threshold: a call on the early schedule that ends above kFgCapQ / 4 candidates per query or
+// re-runs a query sends the index back to the quarter rule (note_i8_early; until
+// cwq_set_filter).  CWQ_FG_I8_EARLY (read per call; tests and A/Bs): 1: the early schedule on
+// an index of any size (building the panel), 0: the quarter rule.
+// CWQ_FG_I8 (read per call; tests and in-process A/Bs):
 // negative: off; n >= 0: from phase n on, building the panel at any size.
 // A launch then takes them only when it is raw (all-uniform, Fast key).
 int fg_i8_from(cwq_index* ix, const int* cuts, int nph, bool cat, bool ib, hipStream_t s) {
@@ -2103,10 +2162,21 @@ int fg_i8_from(cwq_index* ix, const int* cuts, int nph, bool cat, bool ib, hipSt
     const int v = atoi(e);
     return v >= 0 && build_i8(ix, s) ? std::min(v, nph) : nph;
   }
+  const char* ee = getenv("CWQ_FG_I8_EARLY");
+  const int ev = ee && *ee ? atoi(ee) : -1;
+  if ((ev < 0 ? ix->i8_by_size : ev > 0) && ix->n_hub > 0 && !ix->i8_early_off && build_i8(ix, s)) {
+    ix->i8_early_ran = true;
+    return 0;
+  }
   if (ix->i8_state <= 0) return nph;
-  for (int ph = 1; ph < nph; ++ph)   // (never the first launch: it runs on the sample threshold)
+  for (int ph = 1; ph < nph; ++ph)   // (the first launch would run on the strided sample's threshold)
     if (cuts[ph] >= cuts[nph] / 4) return ph;
   return nph;
+}
+
+// After a Fast call on the early schedule: its guard (fg_i8_from).
+void note_i8_early(cwq_index* ix, int64_t nq, int64_t cand_sum, int64_t n_fallback) {
+  if (ix->i8_early_ran && (n_fallback > 0 || cand_sum > nq * (kFgCapQ / 4))) ix->i8_early_off = true;
 }
 
 // CWQ_SELECT_UNFUSED=1: the per-call path keeps select_kernel (and sb_prep) -- A/B only
@@ -2622,7 +2692,10 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
                     hipStream_t s, bool allow_filter) {
   const bool general = k > 64;
   const bool filt = !general && allow_filter && use_filter(ix, k);
-  if (allow_filter) ix->n_fg_i8 = 0;
+  if (allow_filter) {
+    ix->n_fg_i8 = 0;
+    ix->i8_early_ran = false;
+  }
   if (!general && allow_filter && use_filter(ix, k, kStreamMinRows) && use_stream(ix, nq, k))
     return stream_topk_impl(ix, q, nq, k, ids, scores, s);
   const int kl = k <= 16 ? 16 : 64;
@@ -2764,6 +2837,7 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
     if ((rc = rerun_exact(ix, q, redo, k, ids, scores, s))) return rc;
   }
   if (allow_filter) {
+    if (filt) note_i8_early(ix, nq, cand_sum, n_fallback);
     ix->stats[0] = filt ? nq : 0;
     ix->stats[1] = n_fallback;
     ix->stats[2] = filt ? 1 + ((int64_t)std::min(ix->n_fg_i8, 32767) << 16) : 0;   // (<< 16: its int8 launches)
@@ -2837,6 +2911,7 @@ extern "C" int cwq_set_filter(cwq_index* ix, int mode) {
   ix->filt_q = ix->filt_fb = 0;   // a fresh auto-mode record
   ix->filt_auto_off = false;
   ix->filt_off_calls = 0;
+  ix->i8_early_off = false;
   return CWQ_OK;
 }
 

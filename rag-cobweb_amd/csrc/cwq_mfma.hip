@@ -2038,8 +2038,9 @@ hipError_t launch_tighten(int nq, int K, int capq, const int* qcnt, const int* q
 }
 
 // ---------------------------------------------------------------------------
-// final: per query (one wave), T2 = K-th largest l among the candidates, exact keys
-// of the candidates with u >= T2 (bit-identical to the scan kernel's ISO arithmetic),
+// final: per query (one wave), T2 = K-th largest l among the candidates, raised to the
+// K-th largest exact key of the K candidates with the largest l (the seed round), exact
+// keys of the candidates with u >= T2 (bit-identical to the scan kernel's ISO arithmetic),
 // exact top-K into partial-list slot 0.  X is the scan's interleaved query layout
 // [q/16][v][q%16][16].
 // ---------------------------------------------------------------------------
@@ -2188,6 +2189,11 @@ __device__ __forceinline__ float chain_prefix_cached(const float* __restrict__ X
   return P;
 }
 
+#ifndef CWQ_FINAL_SEED   // -DCWQ_FINAL_SEED=0: A/B builds without the seed round (scripts/build_variant.py)
+#define CWQ_FINAL_SEED 1
+#endif
+constexpr bool kFinalSeeded = CWQ_FINAL_SEED != 0;
+
 __global__ __launch_bounds__(256) void final_kernel(const float* __restrict__ X, const float* __restrict__ Mf, int DP,
                                                     int nq, int K, int capq, const int* __restrict__ qcnt,
                                                     const int* __restrict__ qover, const int* __restrict__ crow,
@@ -2230,25 +2236,36 @@ __global__ __launch_bounds__(256) void final_kernel(const float* __restrict__ X,
       const float lv = j < n ? cl[base + j] : -CWQ_INF;
       list64_offer(tk, tr, lane, lv, j, K);
     }
-    const float T2 = rl_f2(tk, K - 1);
-    // pass 2: exact keys of the survivors (u >= T2), packed 64 to a round through a
+    float T2 = rl_f2(tk, K - 1);
+    // seed round: the K candidates of pass 1's list (the largest lower bounds; lane < K
+    // holds one's list position in tr) are scored exactly first, and the K-th largest of
+    // their exact keys raises T2 -- K distinct rows have keys >= it, so it is a valid
+    // threshold, and far nearer the K-th best key than a lower bound is.
+    // pass 2: exact keys of the other survivors (u >= T2), packed 64 to a round through a
     // per-wave LDS list so that every lane of a round has a row (C3: ~20 survivors
     // spread over ~3 chunks of candidates -> one round instead of three)
     int* pend = s_pend[threadIdx.x >> 6];
     int npend = 0;
-    for (int j0 = 0; j0 < n || npend > 0; j0 += 64) {
-      const int j = j0 + lane;
-      const bool c = j < n && cu[base + j] >= T2;
-      const uint64_t bm = __ballot(c);
-      if (c) pend[npend + __popcll(bm & ((1ull << lane) - 1))] = j;
-      npend += __popcll(bm);
-      if (npend < 64 && j0 + 64 < n) continue;   // more candidates to pack first
+    bool seed = kFinalSeeded;
+    for (int j0 = 0; seed || j0 < n || npend > 0;) {
+      if (!seed) {
+        const int j = j0 + lane;
+        bool c = j < n && cu[base + j] >= T2;
+        if (kFinalSeeded)
+          for (int b = 0; b < K; ++b) c = c && j != __builtin_amdgcn_readlane(tr, b);   // scored by the seed round
+        const uint64_t bm = __ballot(c);
+        if (c) pend[npend + __popcll(bm & ((1ull << lane) - 1))] = j;
+        npend += __popcll(bm);
+        j0 += 64;
+        if (npend < 64 && j0 < n) continue;   // more candidates to pack first
+        if (npend == 0) break;
+      }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const bool act = lane < npend;
-      const int jj = act ? pend[lane] : 0;
-      const int rest = npend > 64 ? pend[64 + lane] : 0;   // lane < npend - 64 <= 63
+      const bool act = seed ? lane < K && (unsigned)tr < (unsigned)n : lane < npend;
+      const int jj = act ? (seed ? tr : pend[lane]) : 0;
+      const int rest = !seed && npend > 64 ? pend[64 + lane] : 0;   // lane < npend - 64 <= 63
       float key = -CWQ_INF, lp = 0.f;
       int rid = 0x7fffffff;
       const int rr = act ? crow[base + jj] : 0;
@@ -2296,6 +2313,10 @@ __global__ __launch_bounds__(256) void final_kernel(const float* __restrict__ X,
             lr = sr;
           }
         }
+      }
+      if (seed) {
+        T2 = fmaxf(T2, rl_f2(lk, K - 1));   // (-inf when fewer than K seeds had a row)
+        seed = false;
       }
     }
   }

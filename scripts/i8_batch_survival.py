@@ -17,6 +17,10 @@ query (x 1M / rows) and the fraction of 16-query x 64-row MFMA blocks holding a 
 
 --hybrid adds the table of the policy the batch filter runs (bf16 launches up to a cut of
 the rows, int8 after it; hybrid() below) -- profiles/fgi8_model_c3.log, DESIGN Appendix C.1.
+--hub adds the table of the threshold sample with hub rows (strided + lowest-norm rows) and of
+the first int8 phase, launch by launch with the tighten passes (pipeline() below) --
+profiles/hub_model_c3.log.  With --full equal to --rows the model runs a shape as it is
+(the ratios the tests in tests/test_gpu_hub_sample.py ask for).
 """
 import argparse
 
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--full", type=int, default=1_000_000)
     ap.add_argument("--hybrid", action="store_true", help="also the bf16-then-int8 policy table (hybrid())")
+    ap.add_argument("--hub", action="store_true", help="also the hub-sample / early int8 schedule table (hub())")
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     N, Q, D = args.rows, args.queries, args.dim
@@ -88,6 +93,125 @@ def main():
           f"x{out['int8'][2] / out['bf16'][2]:.2f}", flush=True)
     if args.hybrid:
         hybrid(args, S, dots, Xc, qs, gamma, K)
+    if args.hub:
+        hub(args, S, dots, Xc, qs, gamma, K)
+
+
+def sample_rows(N, norm2, sdiv=128, hub_div=None):
+    """build_filter's threshold sample (cwq_api.hip): S = N/sdiv strided rows (whole 256-row
+    tiles), then H hub rows (lowest |mu'|^2 = largest row term on a flat tree; ties by row
+    index; rows of the strided part skipped), H = S/2 or N/hub_div (0: none; none when
+    N < 4 S), hub j in the 4-row group j mod H/4."""
+    S = min(32768, max(256, N // sdiv // 256 * 256))
+    stride = max(1, N // S)
+    rows = [r for r in (j * stride for j in range(S)) if r < N]
+    H = S // 2 if hub_div is None else (N // hub_div // 256 * 256 if hub_div > 0 else 0)
+    H = min(H, (32768 - len(rows)) // 4 * 4)
+    if N < 4 * S or H <= 0:
+        return np.array(rows), 0
+    seen = set(rows)
+    order = np.lexsort((np.arange(N), norm2))[:H + len(rows)]
+    hubs = [int(r) for r in order if int(r) not in seen][:H]
+    ng = (len(hubs) + 3) // 4
+    rows += [hubs[j] for g in range(ng) for j in range(g, len(hubs), ng)]
+    return np.array(rows), len(hubs)
+
+
+def pipeline(S, wb, w8, wbt, w8t, K, samp, i8_from, cuts=(32, 96, 256, 512)):
+    """The batch filter's launches (run_iso_filter) in S units (smaller = better key): T = the
+    K-th best certified bound of the bf16 sample pass (per 4-row group when the sample has
+    >= 64 K rows), then one launch per row phase -- int8 bounds from phase i8_from on, bf16
+    before -- each followed by the tighten pass (T = K-th best candidate bound so far).
+    Returns per query: candidates, raw records (pretest with the 256-row tile maxima),
+    reranks by the K-th-best-bound rule, reranks by the exact-seeded rule (final_kernel),
+    and the flagged shares of 16x64 blocks and 16x16 sub-blocks of the int8 launches."""
+    Q, N = S.shape
+    sb = (S + wb)[:, samp]
+    if len(samp) >= 64 * K:
+        pad = (-len(samp)) % 4
+        sb = np.pad(sb, ((0, 0), (0, pad)), constant_values=np.inf).reshape(Q, -1, 4).min(2)
+    T = np.partition(sb, K - 1, axis=1)[:, K - 1]
+    n_rt = (N + 255) // 256
+    edges = [0]
+    for f in cuts:
+        c = max(edges[-1] // 256 + 1, n_rt * f // 1024)
+        if c < n_rt:
+            edges.append(c * 256)
+    edges.append(N)
+    cand = np.zeros((Q, N), bool)
+    raw = np.zeros(Q)
+    lo, hi = np.empty((Q, N)), np.empty((Q, N))
+    flag64, flag16, n64, n16 = 0, 0, 0, 0
+    for ph in range(len(edges) - 1):
+        a, b = edges[ph], edges[ph + 1]
+        w, wt = (w8, w8t) if ph >= i8_from else (wb, wbt)
+        lo[:, a:b], hi[:, a:b] = (S - w)[:, a:b], (S + w)[:, a:b]
+        cand[:, a:b] = lo[:, a:b] <= T[:, None]
+        rec = (S - wt)[:, a:b] <= T[:, None]
+        raw += rec.sum(1)
+        if ph >= i8_from:
+            for width in (64, 16):
+                nq_, nr_ = Q // 16, (b - a) // width
+                m = rec[:nq_ * 16, :nr_ * width].reshape(nq_, 16, nr_, width).any(axis=(1, 3))
+                if width == 64:
+                    flag64, n64 = flag64 + m.sum(), n64 + m.size
+                else:
+                    flag16, n16 = flag16 + m.sum(), n16 + m.size
+        kth = np.partition(np.where(cand, hi, np.inf), K - 1, axis=1)[:, K - 1]
+        T = np.minimum(T, kth)
+    hic = np.where(cand, hi, np.inf)
+    t2 = np.partition(hic, K - 1, axis=1)[:, K - 1]
+    rer = (cand & (lo <= t2[:, None])).sum(1)
+    seeds = np.argpartition(hic, K - 1, axis=1)[:, :K]
+    t2s = np.minimum(t2, np.take_along_axis(S, seeds, 1).max(1))
+    notseed = cand.copy()
+    np.put_along_axis(notseed, seeds, False, 1)
+    rer_s = K + (notseed & (lo <= t2s[:, None])).sum(1)
+    return (cand.sum(1), raw, rer, rer_s, flag64 / max(n64, 1), flag16 / max(n16, 1))
+
+
+def hub(args, S, dots, Xc, qs, gamma, K):
+    """Hub rows in the threshold sample and the early int8 schedule: the
+    pipeline() model per sample and first int8 phase -- profiles/hub_model_c3.log."""
+    N, Q = S.shape[1], S.shape[0]
+    scale = args.full / N
+
+    def widths(split, extra):
+        rh, rl = split(Xc.astype(np.float64))
+        xh, xl = split(qs.astype(np.float64))
+        nh, nl = np.linalg.norm(rh, axis=1), np.linalg.norm(rl, axis=1)
+        beta = nl + (gamma * nh if extra is None else 0.0)
+        delta = nh + nl
+        a, c = np.linalg.norm(xh, axis=1)[:, None], np.linalg.norm(xl, axis=1)[:, None]
+        w = 2 * (a * beta[None, :] + c * delta[None, :]) + (0.0 if extra is None else 2 * extra)
+        nt = N // 256 * 256
+        bm = np.repeat(beta[:nt].reshape(-1, 256).max(1), 256)
+        dm = np.repeat(delta[:nt].reshape(-1, 256).max(1), 256)
+        wt = np.full_like(w, np.inf)   # (rows of a last partial tile: always flagged)
+        wt[:, :nt] = 2 * (a * bm[None, :] + c * dm[None, :])
+        return w, np.maximum(w, wt)
+
+    wb, wbt = widths(lambda v: bf16_split(v.astype(np.float32)), None)
+    w8, w8t = widths(i8_split, 2.0 ** -21 * np.abs(dots))
+    norm2 = (Xc.astype(np.float64) ** 2).sum(1)
+    kth = np.partition(S, K - 1, axis=1)[:, K - 1]
+    print(f"hub model, K = {K} of {N} x {Xc.shape[1]} rows, {Q} queries, x{scale:.2f} to {args.full} rows")
+    for name, hd in (("strided", 0), ("strided + hub S/2", None), ("strided + hub 1/128", 128)):
+        samp, nh = sample_rows(N, norm2, hub_div=hd)
+        best = np.partition(S[:, samp], K - 1, axis=1)[:, K - 1]
+        rank = (S < best[:, None]).sum(1) * scale
+        print(f"sample {name}: {len(samp)} rows ({nh} hub); rank of its K-th best key median {np.median(rank):.0f} "
+              f"max {rank.max():.0f}; K-th best key overall in the sample for {100 * (best <= kth).mean():.0f}% of queries")
+    print("| sample | first int8 phase | cand/q | raw records/q | 16x64 blocks | 16x16 sub-blocks | reranks/q bound rule | "
+          "reranks/q exact-seeded |")
+    for name, hd, i8_from in (("strided", 0, 3), ("strided", 0, 0), ("strided + hub S/2", None, 3),
+                              ("strided + hub S/2", None, 1), ("strided + hub S/2", None, 0),
+                              ("strided + hub 1/128", 128, 0), ("strided", 0, 9), ("strided + hub S/2", None, 9)):
+        samp, _ = sample_rows(N, norm2, hub_div=hd)
+        c, raw, rer, rer_s, b64, b16 = pipeline(S, wb, w8, wbt, w8t, K, samp, i8_from)
+        first = {3: "3 (a quarter)", 9: "none (bf16)"}.get(i8_from, str(i8_from))
+        print(f"| {name} | {first} | {c.mean() * scale:.0f} | {raw.mean() * scale:.0f} | {100 * b64:.1f}% | "
+              f"{100 * b16:.1f}% | {rer.mean() * scale:.0f} | {rer_s.mean() * scale:.0f} |", flush=True)
 
 
 def hybrid(args, S, dots, Xc, qs, gamma, K):

@@ -1,0 +1,228 @@
+"""Hub rows in the batch filter's threshold sample and the early int8 schedule (cwq_api.hip
+build_filter / fg_i8_from / note_i8_early).  Every case compares the filter with the exact
+fp32 scan (cwq_set_filter 0): ids AND scores bit-identical.
+
+The sample is the strided rows plus the rows with the largest query-independent key term
+(filter_info()["sample_hub_rows"]; CWQ_FG_HUB_DIV at index creation: 0 none, n NL/n rows).
+An index that got its int8 panel by the size rule runs every launch on the int8 operands
+when its sample holds hub rows; CWQ_FG_I8_EARLY=1 (read per call) gives the small indices
+here that schedule, and a call on it that passes more than 1,024 candidates per query or
+re-runs a query sends the index back to the quarter rule until cwq_set_filter."""
+import os
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+
+@pytest.fixture(scope="module")
+def gpu(pkg):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return pkg
+
+
+def flat_index(pkg, X, hub_div=None):
+    fs = pkg.synth.flat_synth(X)
+    old = os.environ.pop("CWQ_FG_HUB_DIV", None)
+    if hub_div is not None:
+        os.environ["CWQ_FG_HUB_DIV"] = hub_div
+    try:
+        return pkg.index.CobwebIndex(fs["mean"], fs["var"], fs["parent"], fs["node_of_sentence"], device="cuda:0")
+    finally:
+        os.environ.pop("CWQ_FG_HUB_DIV", None)
+        if old is not None:
+            os.environ["CWQ_FG_HUB_DIV"] = old
+
+
+def call(ix, Q, k, mp, knobs):
+    """One call under the given per-call knobs (the filter mode is the caller's) -> ids, scores, stats."""
+    for name in ("CWQ_FG_I8", "CWQ_FG_I8_EARLY"):
+        mp.delenv(name, raising=False)
+    for name, v in knobs.items():
+        mp.setenv(name, v)
+    ids, s = ix.score_topk(Q, k)
+    st = ix.last_stats()
+    for name in knobs:
+        mp.delenv(name)
+    print(knobs, st)
+    assert st["filter_used"] and st["path"] == "fgemm", st
+    return ids.cpu(), s.cpu(), st
+
+
+def filt(ix, Q, k, mp, knobs):
+    ix.set_filter(1)
+    try:
+        return call(ix, Q, k, mp, knobs)
+    finally:
+        ix.set_filter(-1)
+
+
+def exact(ix, Q, k):
+    ix.set_filter(0)
+    ids, s = ix.score_topk(Q, k)
+    assert not ix.last_stats()["filter_used"]
+    ix.set_filter(-1)
+    return ids.cpu(), s.cpu()
+
+
+SHAPES = [(65536, 64), (20000, 768)]
+# Candidates per query, strided sample / strided + hub sample, every launch on the int8
+# operands: scripts/i8_batch_survival.py --hub --rows N --dim D --queries 300 --k k --full N
+# (the CPU model of the launches, not the kernel):
+#   65,536 x 64:  k = 1: 15 / 6,   k = 10: 151 / 81,  k = 64: 873 / 526
+#   20,000 x 768: k = 1: 50 / 13,  k = 10: 413 / 181, k = 64: 1729 / 1182
+# The test asks for half of the model's excess: ratio >= 1 + (model - 1) / 2.
+MODEL_RATIO = {(65536, 64, 1): 15 / 6, (65536, 64, 10): 151 / 81, (65536, 64, 64): 873 / 526,
+               (20000, 768, 1): 50 / 13, (20000, 768, 10): 413 / 181, (20000, 768, 64): 1729 / 1182}
+
+
+@pytest.fixture(scope="module")
+def gaussian(gpu):
+    """Per shape: the index with hub rows, the same index without, 300 queries."""
+    out = {}
+    for N, D in SHAPES:
+        X = gpu.synth.synthetic_corpus(N, D, seed=N + D)
+        Q, _ = gpu.synth.synthetic_queries(X, 300, seed=N)
+        out[N, D] = (flat_index(gpu, X), flat_index(gpu, X, "0"), Q)
+    return out
+
+
+@pytest.mark.parametrize("k", [1, 10, 64])
+@pytest.mark.parametrize("N,D", SHAPES)
+def test_gaussian_early_schedule(gaussian, N, D, k, monkeypatch):
+    ix, ix0, Q = gaussian[N, D]
+    S = max(256, N // 128 // 256 * 256)
+    fi, fi0 = ix.filter_info(), ix0.filter_info()
+    assert fi["sample_hub_rows"] == S // 2 and fi0["sample_hub_rows"] == 0, (fi, fi0)
+    ids0, s0 = exact(ix, Q, k)
+    ids1, s1, st = filt(ix, Q, k, monkeypatch, {"CWQ_FG_I8_EARLY": "1"})
+    assert st["sample_rows"] == S + S // 2, st
+    assert st["fg_i8_launches"] == 5 and st["fallback_queries"] == 0, st
+    assert torch.equal(ids0, ids1) and torch.equal(s0, s1)
+    # the strided sample alone, every launch on the int8 operands too
+    ids2, s2, st0 = filt(ix0, Q, k, monkeypatch, {"CWQ_FG_I8": "0"})
+    assert st0["sample_rows"] == S and st0["fg_i8_launches"] == 5, st0
+    assert torch.equal(ids0, ids2) and torch.equal(s0, s2)
+    need = 1.0 + (MODEL_RATIO[N, D, k] - 1.0) / 2.0
+    print(f"candidates per query: hub sample {st['candidates']}, strided {st0['candidates']}, required x{need:.2f}")
+    assert st0["candidates"] > st["candidates"], (st, st0)
+    assert st0["candidates"] >= need * st["candidates"], (st, st0, need)
+
+
+def test_hub_rows_are_distinct_from_the_strided_rows(gpu, monkeypatch):
+    """33,000 rows: 256 strided rows at stride 128.  Those rows are made the lowest-norm rows
+    of the index, so each of the first 256 hub picks is a strided row and must be skipped: a
+    row counted twice would put T above the K-th best key over distinct rows, and the
+    queries -- all next to the root mean, whose top-64 are those rows -- would lose results."""
+    N, D = 33000, 64
+    X = gpu.synth.synthetic_corpus(N, D, seed=71)
+    X[0:256 * 128:128] *= 0.01
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(72)
+    Q = (X.mean(0)[None, :] + 0.05 * torch.randn((300, D), generator=g, device="cuda:0")).contiguous()
+    ix = flat_index(gpu, X)
+    fi = ix.filter_info()
+    assert fi["sample_hub_rows"] == 128, fi
+    ids0, s0 = exact(ix, Q, 64)
+    for knobs in ({}, {"CWQ_FG_I8_EARLY": "1"}):
+        ids1, s1, st = filt(ix, Q, 64, monkeypatch, knobs)
+        assert st["sample_rows"] - fi["sample_hub_rows"] == 256, (st, fi)
+        assert torch.equal(ids0, ids1) and torch.equal(s0, s1)
+
+
+def test_uninformative_row_terms(gpu, monkeypatch):
+    """Unit-norm rows around a zero mean: every row term is the same, the hub rows are just
+    more sample rows.  The early schedule must still be exact, and its guard, when it trips,
+    brings back the quarter rule until cwq_set_filter."""
+    X = gpu.synth.synthetic_corpus(40000, 64, seed=81)
+    X = X - X.mean(0)[None, :]
+    X = (X / X.norm(dim=1, keepdim=True)).contiguous()
+    Q, _ = gpu.synth.synthetic_queries(X, 300, seed=82)
+    ix = flat_index(gpu, X)
+    assert ix.filter_info()["sample_hub_rows"] == 128
+    ids0, s0 = exact(ix, Q, 10)
+    ix.set_filter(1)
+    try:
+        ids1, s1, st1 = call(ix, Q, 10, monkeypatch, {"CWQ_FG_I8_EARLY": "1"})
+        assert st1["fg_i8_launches"] == 5, st1
+        assert torch.equal(ids0, ids1) and torch.equal(s0, s1)
+        tripped = st1["fallback_queries"] > 0 or st1["candidates"] > 1024
+        ids2, s2, st2 = call(ix, Q, 10, monkeypatch, {"CWQ_FG_I8_EARLY": "1"})
+        assert st2["fg_i8_launches"] == (2 if tripped else 5), (st1, st2)
+        assert torch.equal(ids0, ids2) and torch.equal(s0, s2)
+        ix.set_filter(1)   # a fresh record: the early schedule is tried again
+        ids3, s3, st3 = call(ix, Q, 10, monkeypatch, {"CWQ_FG_I8_EARLY": "1"})
+        assert st3["fg_i8_launches"] == 5, st3
+        assert torch.equal(ids0, ids3) and torch.equal(s0, s3)
+    finally:
+        ix.set_filter(-1)
+
+
+def test_guard_trips_on_a_flood_of_candidates(gpu, monkeypatch):
+    """k = 64 on 20,000 x 768 passes more than 1,024 candidates per query on the int8 operands
+    (the model above: 1,182): the call is exact, and the next one is back on the quarter rule."""
+    X = gpu.synth.synthetic_corpus(20000, 768, seed=91)
+    Q, _ = gpu.synth.synthetic_queries(X, 300, seed=92)
+    ix = flat_index(gpu, X)
+    ids0, s0 = exact(ix, Q, 64)
+    ix.set_filter(1)
+    try:
+        ids1, s1, st1 = call(ix, Q, 64, monkeypatch, {"CWQ_FG_I8_EARLY": "1"})
+        assert st1["fg_i8_launches"] == 5, st1
+        assert torch.equal(ids0, ids1) and torch.equal(s0, s1)
+        tripped = st1["fallback_queries"] > 0 or st1["candidates"] > 1024
+        ids2, s2, st2 = call(ix, Q, 64, monkeypatch, {"CWQ_FG_I8_EARLY": "1"})
+        assert st2["fg_i8_launches"] == (2 if tripped else 5), (st1, st2)
+        assert torch.equal(ids0, ids2) and torch.equal(s0, s2)
+    finally:
+        ix.set_filter(-1)
+
+
+def test_small_index_has_no_hub_rows(gpu, monkeypatch):
+    """NL < 4 S (S = 256): the strided sample already holds more than a quarter of the rows."""
+    X = gpu.synth.synthetic_corpus(1000, 64, seed=101)
+    Q, _ = gpu.synth.synthetic_queries(X, 100, seed=102)
+    ix = flat_index(gpu, X)
+    assert ix.filter_info()["sample_hub_rows"] == 0
+    ids0, s0 = exact(ix, Q, 10)
+    ids1, s1, st = filt(ix, Q, 10, monkeypatch, {"CWQ_FG_I8_EARLY": "1"})
+    assert st["sample_rows"] == 256 and st["fg_i8_launches"] == 0, st   # no hub rows: today's rule, no panel
+    assert torch.equal(ids0, ids1) and torch.equal(s0, s1)
+
+
+def test_group_centred_tree_has_no_hub_rows(gpu, monkeypatch):
+    """Clustered two-level tree (group-centred rows): its sample takes rows of every group."""
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(111)
+    C = 2.0 * torch.randn((100, 64), generator=g, device="cuda:0")
+    lab = torch.randint(0, 100, (30000,), generator=g, device="cuda:0")
+    X = (C[lab] + 0.3 * torch.randn((30000, 64), generator=g, device="cuda:0")).contiguous()
+    Q = (X[:200] + 0.05 * torch.randn((200, 64), generator=g, device="cuda:0")).contiguous()
+    t = gpu.synth.two_level_synth(X, lab)
+    monkeypatch.delenv("CWQ_GROUP_CENTRE", raising=False)
+    ix = gpu.index.CobwebIndex(t["mean"], t["var"], t["parent"], t["node_of_sentence"], device="cuda:0")
+    fi = ix.filter_info()
+    assert fi["group_centred"] and fi["sample_hub_rows"] == 0, fi
+    ids0, s0 = exact(ix, Q, 10)
+    ids1, s1, st = filt(ix, Q, 10, monkeypatch, {})
+    assert torch.equal(ids0, ids1) and torch.equal(s0, s1)
+
+
+def test_two_level_tree_gets_hub_rows(gpu, monkeypatch):
+    """48k N(0, I) rows under 300 random clusters (root-centred rows, parent prefixes in the
+    key): hub rows by the row term alone, no query re-run, the exact scan's results."""
+    X = gpu.synth.synthetic_corpus(48000, 64, seed=121)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(122)
+    t = gpu.synth.two_level_synth(X, torch.randint(0, 300, (X.shape[0],), generator=g, device="cuda:0"))
+    Q, _ = gpu.synth.synthetic_queries(X, 300, seed=123)
+    monkeypatch.delenv("CWQ_GROUP_CENTRE", raising=False)
+    ix = gpu.index.CobwebIndex(t["mean"], t["var"], t["parent"], t["node_of_sentence"], device="cuda:0")
+    fi = ix.filter_info()
+    assert not fi["group_centred"] and fi["sample_hub_rows"] == 128, fi
+    ids0, s0 = exact(ix, Q, 10)
+    ids1, s1, st = filt(ix, Q, 10, monkeypatch, {})
+    assert st["sample_rows"] == 256 + 128 and st["fallback_queries"] == 0, st
+    assert torch.equal(ids0, ids1) and torch.equal(s0, s1)
