@@ -169,6 +169,35 @@ int cwq_rank_scores_backward(cwq_index* idx, const float* q, int64_t nq, const f
                              void* stream);
 
 /*
+ * Cross-entropy ranking loss over ALL sentence scores, its gradient, and the target's score
+ * and rank, without a [nq*n_sent] array on either side of this call.  Replaces the loop of
+ * FixedDocsRankingLoss.forward (src/training/cobweb_query_train.py:104-126:
+ * cobweb_rank_scores -> CrossEntropyLoss(scores / temperature, label) per query) and the
+ * per-query numbers of evaluate() (:213-304: the true document's score and its position in a
+ * full argsort).
+ *   q            device [nq*dim] fp32
+ *   target       device [nq] int64 sentence ids (the reference's labels: columns of
+ *                cobweb_rank_scores)
+ *   temperature  finite, > 0
+ *   loss         device [nq]: logsumexp_s(score[q][s] / T) - score[q][target[q]] / T over the
+ *                sentences in the tree (the others score -inf and add nothing, as in torch);
+ *                per query, not reduced
+ *   grad_q       device [nq*dim]: d loss[q] / d q[q][:]; NULL: forward only (no backward pass)
+ *   target_score device [nq] or NULL: the target's score, the bits cwq_rank_scores writes
+ *   rank         device [nq] int64 or NULL: 1 + the number of sentences before the target in
+ *                cwq_score_topk's order (higher score, then lower node index, then lower
+ *                sentence id), so rank <= k exactly when cwq_score_topk(k) returns the target
+ * A target outside [0, n_sent) or whose sentence is not in the tree: loss +inf, a zero grad_q
+ * row, target_score -inf, rank -1 (torch: inf / NaN); the other queries are not affected.
+ * No float atomics: identical from run to run, and a query's outputs do not depend on the
+ * other queries of the call or on the workspace chunking.  CWQ_ERR_ARG before any device
+ * work for a NULL idx / q / target / loss, nq < 0, or a temperature that is not finite and
+ * > 0; nq == 0 is a no-op.  Keeps no state between calls.
+ */
+int cwq_rank_ce(cwq_index* idx, const float* q, int64_t nq, const int64_t* target, float temperature,
+                float* loss, float* grad_q, float* target_score, int64_t* rank, void* stream);
+
+/*
  * Per-node Gaussian log-likelihood for every node in BFS order.
  *   full = 0: lp'(n) as CobwebWrapper.py:232-236 (no 2*pi term)
  *   full = 1: CobwebTorchNode.log_prob (CobwebTorchNode.py:100-104, with 2*pi)

@@ -37,6 +37,7 @@ SIGNATURES = {
     "cwq_score_topk": (_c.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "cwq_rank_scores": (_c.c_int, [_P, _P, _I64, _P, _P]),
     "cwq_rank_scores_backward": (_c.c_int, [_P, _P, _I64, _P, _P, _P]),
+    "cwq_rank_ce": (_c.c_int, [_P, _P, _I64, _P, _c.c_float, _P, _P, _P, _P, _P]),
     "cwq_node_logprob": (_c.c_int, [_P, _P, _I64, _I32, _P, _P]),
     "cwq_prefix_bounds": (_c.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
     "cwq_categorize": (_c.c_int, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P]),

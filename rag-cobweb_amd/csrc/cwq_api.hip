@@ -381,7 +381,7 @@ struct WsUse {
 #ifndef CWQ_BUILD_ID
 #define CWQ_BUILD_ID "unversioned"
 #endif
-extern "C" int cwq_version(void) { return 200; }
+extern "C" int cwq_version(void) { return 300; }
 // "CWQ_BUILD_ID=<id>" is also searched for in the file by build.py (no dlopen needed)
 static const char kBuildId[] = "CWQ_BUILD_ID=" CWQ_BUILD_ID;
 extern "C" const char* cwq_build_id(void) { return kBuildId + 13; }
@@ -2981,6 +2981,118 @@ extern "C" int cwq_rank_scores(cwq_index* ix, const float* q, int64_t nq, float*
   return CWQ_OK;
 }
 
+namespace {
+
+// The backward's launch plan: slabs, leaf-sum pieces, threads per node and workspace bytes per
+// query -- functions of the index alone (a query's gradient is the same in any batch).
+struct GradPlan {
+  int rps, ns_iso, ns_an, ns_int, nslab, nsplit, P;
+  std::vector<int> lv;
+  size_t per_q;
+};
+
+GradPlan grad_plan(const cwq_index* ix) {
+  GradPlan g;
+  const int NL = ix->NL, NI = ix->NI;
+  g.rps = grad_rows_per_slab((int64_t)ix->NL_iso + 2 * ((int64_t)ix->NL_an + NI), ix->cus);
+  g.ns_iso = (ix->NL_iso + g.rps - 1) / g.rps;
+  g.ns_an = (ix->NL_an + g.rps - 1) / g.rps;
+  g.ns_int = (NI + g.rps - 1) / g.rps;
+  g.nslab = g.ns_iso + g.ns_an + g.ns_int;
+  g.nsplit = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)ix->max_fanout + 4095) / 4096));
+  g.P = ix->max_fanout > 64 ? 16 : 1;
+  for (auto& l : ix->levels) {
+    g.lv.push_back(l.first);
+    g.lv.push_back(l.second);
+  }
+  g.per_q = ((size_t)2 * std::max(NL, 1) + (size_t)(2 + g.nsplit) * std::max(NI, 1) + (size_t)g.nslab * ix->DP) * 4;
+  return g;
+}
+
+// The coefficient arrays and the partial tiles of one chunk (nq16 * per_q bytes + 8 * 256).
+float* grad_carve(const cwq_index* ix, const GradPlan& gp, Bump& b, int nqc, int qtiles, GradCoefArgs& ca) {
+  const int NL = ix->NL, NI = ix->NI;
+  const size_t nq16 = (size_t)qtiles * kXQ;
+  memset(&ca, 0, sizeof(ca));
+  ca.n_sent = ix->n_sent;
+  ca.nq = nqc;
+  ca.qtiles = qtiles;
+  ca.NL = NL;
+  ca.NL_iso = ix->NL_iso;
+  ca.NI = NI;
+  ca.sent_ptr = ix->sent_ptr;
+  ca.sent_ids = ix->sent_ids;
+  ca.meta = ix->row_meta;
+  ca.leaf_a0 = ix->int_leaf_a0;
+  ca.leaf_a1 = ix->int_leaf_a1;
+  ca.leaf_b0 = ix->int_leaf_b0;
+  ca.leaf_b1 = ix->int_leaf_b1;
+  ca.child_begin = ix->int_child_begin;
+  ca.child_end = ix->int_child_end;
+  ca.w_int = ix->w_int;
+  ca.lv = gp.lv.data();
+  ca.nlev = (int)ix->levels.size();
+  ca.P = gp.P;
+  ca.nsplit = gp.nsplit;
+  ca.coefL = b.take<float>(nq16 * std::max(NL, 1));
+  ca.hL = b.take<float>(nq16 * std::max(NL, 1));
+  ca.cz = b.take<float>(nq16 * std::max(NI, 1) * gp.nsplit);
+  ca.cI = b.take<float>(nq16 * std::max(NI, 1));
+  ca.coefI = b.take<float>(nq16 * std::max(NI, 1));
+  return b.take<float>(nq16 * (size_t)gp.nslab * ix->DP);
+}
+
+// The streaming reduction over the three row classes and the slab sum, from the coefficients.
+int grad_streams(const cwq_index* ix, const GradPlan& gp, const GradCoefArgs& ca, float* part, const float* q, int nqc,
+                 int qtiles, float* grad_q, hipStream_t s) {
+  const int NL = ix->NL, NI = ix->NI, DP = ix->DP;
+  GradStreamArgs g;
+  memset(&g, 0, sizeof(g));
+  g.q = q;
+  g.nq = nqc;
+  g.qtiles = qtiles;
+  g.D = ix->D;
+  g.DP = DP;
+  g.rows_per_slab = gp.rps;
+  g.part = part;
+  if (ix->NL_iso > 0) {   // isotropic rows: row-major fp32 means, 1/v folded into the coefficient
+    g.M = ix->iso_Mf;
+    g.nrows = ix->NL_iso;
+    g.coef = ca.coefL;
+    g.ncoef = NL;
+    g.coef_base = 0;
+    g.slab_off = 0;
+    HIPCHK(launch_grad_stream(g, s));
+  }
+  g.M = nullptr;
+  if (ix->NL_an > 0) {
+    g.A = ix->an_A;
+    g.B = ix->an_B;
+    g.ld = ix->ld_an;
+    g.nrows = ix->NL_an;
+    g.coef = ca.coefL;
+    g.ncoef = NL;
+    g.coef_base = ix->NL_iso;
+    g.slab_off = gp.ns_iso;
+    HIPCHK(launch_grad_stream(g, s));
+  }
+  if (NI > 0) {
+    g.A = ix->int_A;
+    g.B = ix->int_B;
+    g.ld = ix->ld_int;
+    g.nrows = NI;
+    g.coef = ca.coefI;
+    g.ncoef = NI;
+    g.coef_base = 0;
+    g.slab_off = gp.ns_iso + gp.ns_an;
+    HIPCHK(launch_grad_stream(g, s));
+  }
+  HIPCHK(launch_grad_reduce(part, gp.nslab, qtiles, nqc, DP, ix->D, grad_q, s));
+  return CWQ_OK;
+}
+
+}  // namespace
+
 // Backward of cwq_rank_scores (cwq_grad.hip): the coefficient pass, the streaming reduction
 // over the three row classes, the slab sum.  Needs q, grad_out and the index only.
 extern "C" int cwq_rank_scores_backward(cwq_index* ix, const float* q, int64_t nq, const float* grad_out,
@@ -2993,99 +3105,94 @@ extern "C" int cwq_rank_scores_backward(cwq_index* ix, const float* q, int64_t n
   hipStream_t s = (hipStream_t)stream;
   WsUse wu(ix, s);
   if (wu.rc) return wu.rc;
-  const int NL = ix->NL, NI = ix->NI, DP = ix->DP;
-  // slabs: a function of the index alone (a query's gradient is the same in any batch)
-  const int rps = grad_rows_per_slab((int64_t)ix->NL_iso + 2 * ((int64_t)ix->NL_an + NI), ix->cus);
-  const int ns_iso = (ix->NL_iso + rps - 1) / rps, ns_an = (ix->NL_an + rps - 1) / rps, ns_int = (NI + rps - 1) / rps;
-  const int nslab = ns_iso + ns_an + ns_int;
-  const int nsplit = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)ix->max_fanout + 4095) / 4096));
-  const int P = ix->max_fanout > 64 ? 16 : 1;
-  std::vector<int> lv;
-  for (auto& l : ix->levels) {
-    lv.push_back(l.first);
-    lv.push_back(l.second);
-  }
-  const size_t per_q = ((size_t)2 * std::max(NL, 1) + (size_t)(2 + nsplit) * std::max(NI, 1) + (size_t)nslab * DP) * 4;
-  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, per_q, false), 4096);
+  const GradPlan gp = grad_plan(ix);
+  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, gp.per_q, false), 4096);
   int rc;
   for (int64_t q0 = 0; q0 < nq; q0 += cq) {
     const int nqc = (int)std::min(cq, nq - q0);
     const int qtiles = (nqc + kXQ - 1) / kXQ;
     const size_t nq16 = (size_t)qtiles * kXQ;
-    if ((rc = ix->reserve(nq16 * per_q + 8 * 256))) return rc;
+    if ((rc = ix->reserve(nq16 * gp.per_q + 8 * 256))) return rc;
     Bump b(ix->ws, ix->ws_size);
     GradCoefArgs ca;
-    memset(&ca, 0, sizeof(ca));
+    float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
     ca.G = grad_out + q0 * ix->n_sent;
-    ca.n_sent = ix->n_sent;
-    ca.nq = nqc;
-    ca.qtiles = qtiles;
-    ca.NL = NL;
-    ca.NL_iso = ix->NL_iso;
-    ca.NI = NI;
-    ca.sent_ptr = ix->sent_ptr;
-    ca.sent_ids = ix->sent_ids;
-    ca.meta = ix->row_meta;
-    ca.leaf_a0 = ix->int_leaf_a0;
-    ca.leaf_a1 = ix->int_leaf_a1;
-    ca.leaf_b0 = ix->int_leaf_b0;
-    ca.leaf_b1 = ix->int_leaf_b1;
-    ca.child_begin = ix->int_child_begin;
-    ca.child_end = ix->int_child_end;
-    ca.w_int = ix->w_int;
-    ca.lv = lv.data();
-    ca.nlev = (int)ix->levels.size();
-    ca.P = P;
-    ca.nsplit = nsplit;
-    ca.coefL = b.take<float>(nq16 * std::max(NL, 1));
-    ca.hL = b.take<float>(nq16 * std::max(NL, 1));
-    ca.cz = b.take<float>(nq16 * std::max(NI, 1) * nsplit);
-    ca.cI = b.take<float>(nq16 * std::max(NI, 1));
-    ca.coefI = b.take<float>(nq16 * std::max(NI, 1));
-    float* part = b.take<float>(nq16 * (size_t)nslab * DP);
     HIPCHK(launch_grad_coef(ca, s));
-    GradStreamArgs g;
-    memset(&g, 0, sizeof(g));
-    g.q = q + q0 * ix->D;
-    g.nq = nqc;
-    g.qtiles = qtiles;
-    g.D = ix->D;
-    g.DP = DP;
-    g.rows_per_slab = rps;
-    g.part = part;
-    if (ix->NL_iso > 0) {   // isotropic rows: row-major fp32 means, 1/v folded into the coefficient
-      g.M = ix->iso_Mf;
-      g.nrows = ix->NL_iso;
-      g.coef = ca.coefL;
-      g.ncoef = NL;
-      g.coef_base = 0;
-      g.slab_off = 0;
-      HIPCHK(launch_grad_stream(g, s));
-    }
-    g.M = nullptr;
-    if (ix->NL_an > 0) {
-      g.A = ix->an_A;
-      g.B = ix->an_B;
-      g.ld = ix->ld_an;
-      g.nrows = ix->NL_an;
-      g.coef = ca.coefL;
-      g.ncoef = NL;
-      g.coef_base = ix->NL_iso;
-      g.slab_off = ns_iso;
-      HIPCHK(launch_grad_stream(g, s));
-    }
-    if (NI > 0) {
-      g.A = ix->int_A;
-      g.B = ix->int_B;
-      g.ld = ix->ld_int;
-      g.nrows = NI;
-      g.coef = ca.coefI;
-      g.ncoef = NI;
-      g.coef_base = 0;
-      g.slab_off = ns_iso + ns_an;
-      HIPCHK(launch_grad_stream(g, s));
-    }
-    HIPCHK(launch_grad_reduce(part, nslab, qtiles, nqc, DP, ix->D, grad_q + q0 * ix->D, s));
+    if ((rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
+  }
+  return CWQ_OK;
+}
+
+// Cross-entropy ranking loss over all sentence scores with its gradient, the target's score
+// and rank (cwq_loss.hip): the exact scan's row keys stay in the workspace,
+// the softmax goes straight into the backward's coefficient layout.
+extern "C" int cwq_rank_ce(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
+                           float* loss, float* grad_q, float* target_score, int64_t* rank, void* stream) {
+  if (!ix || !q || !target || !loss) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
+  if (!std::isfinite(temperature) || !(temperature > 0.f))
+    return fail(CWQ_ERR_ARG, "temperature must be finite and > 0");
+  if (nq == 0) return CWQ_OK;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DevGuard dg(ix->device);
+  hipStream_t s = (hipStream_t)stream;
+  WsUse wu(ix, s);
+  ScanCfgScope scs(nq);
+  if (wu.rc) return wu.rc;
+  const int NL = ix->NL;
+  const int npart = (NL + kCePart - 1) / kCePart;
+  const GradPlan gp = grad_plan(ix);
+  // per query: its row keys, the partials and (m, 1/z, row); the backward's arrays when wanted
+  const size_t ce_q = (size_t)std::max(npart, 1) * 12 + 12;
+  const size_t per_q = (size_t)std::max(NL, 1) * 4 + ce_q + (grad_q ? gp.per_q : 0);
+  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, per_q, false), 4096);
+  int rc;
+  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
+    const int nqc = (int)std::min(cq, nq - q0);
+    const int64_t nq_pad = round_up(nqc, kQPad);
+    const int qtiles = (nqc + kXQ - 1) / kXQ;
+    const size_t nq16 = (size_t)qtiles * kXQ;
+    if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(NL, 1) * 4 + nq16 * ce_q +
+                          (grad_q ? nq16 * gp.per_q : 0) + 24 * 256)))
+      return rc;
+    Bump b(ix->ws, ix->ws_size);
+    Chunk c;
+    carve_chunk(ix, b, c, nqc, false);
+    float* rowkey = b.take<float>((size_t)nq_pad * std::max(NL, 1));
+    CeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rowkey = rowkey;
+    a.ldr = NL;
+    a.NL = NL;
+    a.nq = nqc;
+    a.qtiles = qtiles;
+    a.npart = npart;
+    a.invT = 1.f / temperature;
+    a.sent_ptr = ix->sent_ptr;
+    a.sent_ids = ix->sent_ids;
+    a.row_bfs = ix->row_bfs;
+    a.row_of_sent = ix->row_of_sent;
+    a.n_sent = ix->n_sent;
+    a.target = target + q0;
+    a.pm = b.take<float>(nq16 * std::max(npart, 1));
+    a.pz = b.take<float>(nq16 * std::max(npart, 1));
+    a.pc = b.take<int>(nq16 * std::max(npart, 1));
+    a.mz = b.take<float2>(nq16);
+    a.rtq = b.take<int>(nq16);
+    a.loss = loss + q0;
+    a.tscore = target_score ? target_score + q0 : nullptr;
+    a.rank = rank ? rank + q0 : nullptr;
+    HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
+    if ((rc = run_internal(ix, c, s, false))) return rc;
+    if ((rc = run_leaf_scan(ix, c, EPI_KEY, false, 16, 0.f, rowkey, NL, nullptr, nullptr, nullptr, 1, nullptr, s)))
+      return rc;
+    HIPCHK(launch_ce_reduce(a, s));
+    if (!grad_q) continue;
+    GradCoefArgs ca;
+    float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
+    HIPCHK(launch_ce_coef(a, ix->row_meta, ix->NL_iso, ca.coefL, ca.hL, s));
+    HIPCHK(launch_grad_tree(ca, s));
+    if ((rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
   }
   return CWQ_OK;
 }

@@ -395,14 +395,20 @@ int grad_rows_per_slab(int64_t weighted_rows, int cus) {
   return (int)((s + 7) / 8 * 8);
 }
 
+hipError_t launch_grad_rows(const GradCoefArgs& a, hipStream_t s) {
+  if (a.NL <= 0) return hipSuccess;
+  hipLaunchKernelGGL(grad_rows_kernel, dim3((unsigned)((a.NL + 63) / 64), (unsigned)a.qtiles), dim3(256), 0, s, a.G,
+                     a.n_sent, a.nq, a.sent_ptr, a.sent_ids, a.meta, a.NL, a.NL_iso, a.coefL, a.hL);
+  return hipGetLastError();
+}
+
 hipError_t launch_grad_coef(const GradCoefArgs& a, hipStream_t s) {
+  const hipError_t e = launch_grad_rows(a, s);
+  return e != hipSuccess ? e : launch_grad_tree(a, s);
+}
+
+hipError_t launch_grad_tree(const GradCoefArgs& a, hipStream_t s) {
   const dim3 blk(256);
-  if (a.NL > 0) {
-    hipLaunchKernelGGL(grad_rows_kernel, dim3((unsigned)((a.NL + 63) / 64), (unsigned)a.qtiles), blk, 0, s, a.G,
-                       a.n_sent, a.nq, a.sent_ptr, a.sent_ids, a.meta, a.NL, a.NL_iso, a.coefL, a.hL);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
   if (a.NI <= 0) return hipSuccess;
   const int P = a.P;
   const unsigned nb = (unsigned)(P == 16 ? a.NI : (a.NI + 15) / 16);

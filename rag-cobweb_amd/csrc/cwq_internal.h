@@ -920,7 +920,11 @@ struct GradCoefArgs {
   float* cz;                  // [nsplit][qtiles][NI][16]
   float* cI; float* coefI;    // [qtiles][NI][16]: c, w_int c
 };
-hipError_t launch_grad_coef(const GradCoefArgs& a, hipStream_t s);
+hipError_t launch_grad_coef(const GradCoefArgs& a, hipStream_t s);   // the row step, then the tree step
+// its two steps: G -> coefL / hL (grad_rows_kernel), and hL -> coefI (leaf sums + levels); the
+// fused loss (cwq_loss.hip) writes coefL / hL itself and runs only the tree step
+hipError_t launch_grad_rows(const GradCoefArgs& a, hipStream_t s);
+hipError_t launch_grad_tree(const GradCoefArgs& a, hipStream_t s);
 // One row class of the streaming reduction: isotropic rows (M row-major [nrows][DP], term
 // coef (x - mu)) or dim-major A / B [DP][ld] (term coef A (x A - B)); partial tiles
 // part[slab_off + slab][qtiles * 16][DP] for the valid queries.
@@ -938,6 +942,24 @@ hipError_t launch_grad_reduce(const float* part, int nslab, int qtiles, int nq, 
 // rows per slab for `weighted_rows` rows of stream (three slabs per CU, at least 256 rows):
 // a function of the index alone, so a query's gradient does not depend on the batch
 int grad_rows_per_slab(int64_t weighted_rows, int cus);
+
+// ---- cross-entropy ranking loss over all sentence scores (cwq_loss.hip) ----
+constexpr int kCePart = 2048;   // rows per (m, z, count) partial: a function of the index alone
+struct CeArgs {
+  const float* rowkey; int64_t ldr;   // [nq][ldr] exact row keys (run_leaf_scan, EPI_KEY)
+  int NL, nq, qtiles, npart;          // npart = ceil(NL / kCePart)
+  float invT;
+  const int64_t* sent_ptr; const int64_t* sent_ids; const int* row_bfs; const int* row_of_sent;
+  int64_t n_sent;
+  const int64_t* target;              // [nq] sentence ids
+  float* pm; float* pz; int* pc;      // [qtiles * 16][npart] partials
+  float* loss; float* tscore; int64_t* rank;   // [nq]; tscore / rank may be null
+  float2* mz; int* rtq;               // [qtiles * 16]: (m, 1/z), the target's row (-1: invalid)
+};
+// ce_part_kernel + ce_final_kernel: the partials, then loss / tscore / rank / mz / rtq
+hipError_t launch_ce_reduce(const CeArgs& a, hipStream_t s);
+// ce_coef_kernel: coefL / hL [qtiles][NL][16] of the loss's gradient (grad_rows_kernel's layout)
+hipError_t launch_ce_coef(const CeArgs& a, const RowMeta* meta, int NL_iso, float* coefL, float* hL, hipStream_t s);
 
 // PCA + ICA whitening (cwq_whiten.hip): C[m][n] = sum_k (A[m][k] - ctr[k]) B[n][k] (/ denom[n])
 hipError_t launch_gemm_nt_f32(const float* A, int64_t M, int K, const float* ctr, const float* B, int N,

@@ -331,6 +331,34 @@ class CobwebIndex:
                                                    _stream(self.device)))
         return out
 
+    def rank_ce(self, q, target, temperature=1.0, grad=False):
+        """Cross-entropy ranking loss over all sentence scores (cwq_rank_ce): q [nq, dim],
+        target [nq] sentence ids -> (loss [nq] = logsumexp(scores / T) - scores[target] / T,
+        grad_q [nq, dim] = d loss / d q or None when grad is False, target_score [nq], rank [nq]
+        int64: the target's 1-based position in score_topk's order).  No [nq, n_sent] tensor is
+        made.  A target outside the tree: loss inf, a zero gradient row, score -inf, rank -1."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        t = torch.as_tensor(target)
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError("target must hold integer sentence ids")
+        t = t.reshape(-1).to(self.device, torch.int64).contiguous()
+        if t.shape[0] != nq:
+            raise ValueError(f"target must be [{nq}]")
+        temperature = float(temperature)
+        if not (np.isfinite(temperature) and temperature > 0):
+            raise ValueError("temperature must be finite and > 0")
+        loss = torch.empty(nq, dtype=torch.float32, device=self.device)
+        tscore = torch.empty(nq, dtype=torch.float32, device=self.device)
+        rank = torch.empty(nq, dtype=torch.int64, device=self.device)
+        gq = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device) if grad else None
+        if nq == 0:   # empty tensors have no device pointer to pass
+            return loss, gq, tscore, rank
+        with torch.cuda.device(self.device):
+            check(self._L.cwq_rank_ce(self._h, _ptr(q), nq, _ptr(t), temperature, _ptr(loss),
+                                      _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank), _stream(self.device)))
+        return loss, gq, tscore, rank
+
     def node_logprob(self, q, full=False):
         """Per-node log-likelihood in BFS order: lp' (full=False) or log_prob (full=True)."""
         q = self._queries(q)

@@ -305,6 +305,29 @@ class CobwebWrapper:
         self.build_prediction_index()
         return self._index.rank_scores(queries)
 
+    def cobweb_ranking_loss(self, queries, labels, temperature=1.0, reduction="mean"):
+        """FixedDocsRankingLoss.forward (src/training/cobweb_query_train.py:104-126) for a
+        block: [Q, D] query embeddings and [Q] labels (sentence ids) -> CrossEntropyLoss(
+        cobweb_rank_scores(q) / temperature, label) averaged over the batch ("mean", the
+        reference), summed ("sum") or per query ("none").  Differentiable with respect to
+        `queries`; the scores are never materialised (cwq_rank_ce: one forward scan, and one
+        backward stream when a gradient is wanted)."""
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError('reduction must be "mean", "sum" or "none"')
+        self.build_prediction_index()
+        from .autograd import rank_ce_autograd
+        loss, _, _ = rank_ce_autograd(self._index, torch.as_tensor(queries), labels, temperature)
+        return loss if reduction == "none" else loss.mean() if reduction == "mean" else loss.sum()
+
+    def cobweb_target_ranks(self, queries, labels):
+        """evaluate()'s two per-query numbers (src/training/cobweb_query_train.py:213-304)
+        without forming a ranking: (rank [Q] int64, the 1-based position of the label in the
+        Fast ranking -- -1 for a label outside the tree --, true_score [Q])."""
+        self.build_prediction_index()
+        with torch.no_grad():
+            _, _, tscore, rank = self._index.rank_ce(torch.as_tensor(queries).detach(), labels)
+        return rank, tscore
+
     def cobweb_predict(self, input, k=5, return_ids=False, is_embedding=False):
         """CobwebWrapper.py:435-461 ("Cobweb Basic"): best-first categorize with
         retrieve_k=k and max_nodes=max_init_search; IndexError when fewer than k

@@ -9,6 +9,13 @@ Prints, per nq, the HIP-event times and the mean-stream rate rows * DP * 4 bytes
 each pass as a fraction of the achievable HBM rate (6.3 TB/s), and for comparison the time of
 torch autograd through a dense torch restatement of CobwebWrapper.py:283-292 (what a user
 would otherwise run) at --torch-n rows on the same GPU.
+
+    python scripts/grad_probe.py --ce --n 1000000 --nq 1,16,256
+
+--ce measures the fused ranking loss instead (cwq_rank_ce), in this one
+process: per nq the median [min, max] of --reps alternating runs of (a) rank_scores with grad ->
+F.cross_entropy(reduction="sum") -> backward, (b) rank_ce with its gradient, (c) the
+forward-only pair, and the peak of torch.cuda.max_memory_allocated() across (a) and across (b).
 """
 import argparse
 import os
@@ -52,6 +59,80 @@ def torch_dense(fs, Q, n, reps):
     return {nq: event_ms(lambda: step(nq), reps) for nq in (1, 16)}
 
 
+def event_all(fns, reps):
+    """Per function (median, min, max) of reps HIP-event timings, the functions taking turns
+    inside every repetition (drift of the box hits them alike), after one warm-up call each."""
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[i].append(a.elapsed_time(b))
+    return [(sorted(t)[len(t) // 2], min(t), max(t)) for t in ts]
+
+
+def peak_mb(fn):
+    """Peak of torch's allocator over one call of fn, above what is allocated before it (the
+    library's own workspace is not torch memory: reported separately)."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+def ce_probe(ix, Q, nqs, reps, T, tag):
+    """--ce: the training step's loss through (a) rank_scores with grad -> F.cross_entropy ->
+    backward, (b) the fused rank_ce with its gradient, and (c) rank_ce forward only against
+    rank_scores + a count of the scores above the target's; peak torch memory of (a) and (b)."""
+    F = torch.nn.functional
+    dev = ix.device
+    gen = torch.Generator(device=dev).manual_seed(7)
+    for nq in nqs:
+        q = Q[:nq].contiguous()
+        labels = torch.randint(0, ix.n_sent, (nq,), device=dev, generator=gen)
+
+        def a():
+            x = q.clone().requires_grad_()
+            F.cross_entropy(ix.rank_scores(x) / T, labels, reduction="sum").backward()
+            return x.grad
+
+        def b():
+            return ix.rank_ce(q, labels, T, grad=True)
+
+        def c_old():
+            s = ix.rank_scores(q)
+            return (s > s.gather(1, labels[:, None])).sum(1)
+
+        def c_new():
+            return ix.rank_ce(q, labels, T)
+
+        ga, (lb, gb, _, rb) = a(), b()
+        rel = float(((ga - gb).double().norm(dim=1) / ga.double().norm(dim=1)).max())
+        assert bool((c_old() + 1 <= rb).all())   # the count above, plus ties before the target
+        ta, tb, tco, tcn = event_all((a, b, c_old, c_new), reps)
+        # the unfused path's spread and the fused path's, each as (max - min) / median
+        spread = max((ta[2] - ta[1]) / ta[0], (tb[2] - tb[1]) / tb[0])
+        verdict = "neutral (within the spread)" if abs(ta[0] - tb[0]) <= spread * ta[0] else \
+            ("fused faster" if tb[0] < ta[0] else "FUSED SLOWER")
+        pa, pb = peak_mb(a), peak_mb(b)
+        print(f"rank_ce {tag} nq={nq} T={T:g}: (a) rank_scores+cross_entropy fwd+bwd {ta[0]:.3f} ms "
+              f"[{ta[1]:.3f}, {ta[2]:.3f}]  (b) rank_ce fwd+bwd {tb[0]:.3f} ms [{tb[1]:.3f}, {tb[2]:.3f}]  "
+              f"b/a {tb[0] / ta[0]:.3f}, spread {spread:.1%}: {verdict}", flush=True)
+        print(f"rank_ce {tag} nq={nq}: (c) forward only: rank_scores + count {tco[0]:.3f} ms "
+              f"[{tco[1]:.3f}, {tco[2]:.3f}]  rank_ce {tcn[0]:.3f} ms [{tcn[1]:.3f}, {tcn[2]:.3f}]", flush=True)
+        print(f"rank_ce {tag} nq={nq}: peak torch memory above the inputs (a) {pa:.1f} MiB  (b) {pb:.3f} MiB; "
+              f"grad (a) vs (b) max rel L2 {rel:.3g}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -59,6 +140,10 @@ def main():
     ap.add_argument("--nq", default="1,16")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--torch-n", type=int, default=100_000)
+    ap.add_argument("--ce", action="store_true", help="the fused ranking loss (rank_ce) against rank_scores + "
+                    "torch cross_entropy, in this one process")
+    ap.add_argument("--temperature", type=float, default=0.0, help="--ce: 0 = the standard deviation of the "
+                    "first query's scores")
     args = ap.parse_args()
     pkg = cobweb_pkg.load()
     dev = torch.device("cuda", 0)
@@ -67,6 +152,14 @@ def main():
     nqs = [int(v) for v in args.nq.split(",")]
     Q, _ = pkg.synth.synthetic_queries(X, max(max(nqs), 16), seed=1)
     del X
+    if args.ce:
+        ix = pkg.index.CobwebIndex(fs["mean"], fs["var"], fs["parent"], fs["node_of_sentence"], device=dev)
+        del fs
+        torch.cuda.empty_cache()
+        T = args.temperature or float(ix.rank_scores(Q[:1]).std())
+        ce_probe(ix, Q, nqs, args.reps, T, f"n={args.n} d={args.dim}")
+        print("done", flush=True)
+        return
     tn = min(args.torch_n, args.n)
     tt = torch_dense(fs, Q, tn, 3)
     ix = pkg.index.CobwebIndex(fs["mean"], fs["var"], fs["parent"], fs["node_of_sentence"], device=dev)
