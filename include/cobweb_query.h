@@ -409,6 +409,39 @@ int cwq_mt19937_skip(uint32_t* state625, int64_t nwords);
 int cwq_whiten(const float* X, int64_t n, int32_t d_in, const float* mean, const float* comps, int32_t d_pca,
                const float* denom, const float* unmix, int32_t d_out, float* out, float* work, void* stream);
 
+/*
+ * Whitening fits on the GPU: the row-proportional passes of PCAICAWhiteningModel.fit
+ * (src/whitening/pca_ica.py:55-76: the mean :59, PCA :63-66, FastICA :72-74),
+ * ZCAWhiteningModel.fit (src/whitening/zca.py:32-51: mean :36, np.cov :40) and
+ * PCAZCAWhiteningModel.fit (src/whitening/pca_zca.py:47-60).  The small d x d algebra
+ * (eigh, FastICA's symmetric decorrelation) stays with the caller, in fp64.
+ *
+ * All three are handle-less and stream-ordered, accumulate INTO their fp64 outputs (the
+ * caller zeroes them and may call repeatedly over row chunks), take scratch from the
+ * caller (`*_work_bytes`; -1 for a bad shape) and use no atomics: rows are cut into
+ * fixed slabs (cwq_whitenfit_slab() rows; 128-row tiles for gsum), each slab is summed
+ * on its own (the GEMMs in fp32 on v_mfma_f32_32x32x2_f32) and the slab partials are
+ * added in slab order in fp64, so results are bit-identical from run to run on any
+ * device.  Dimensions are in [1, 1024]; n == 0 is a no-op; bad arguments return
+ * CWQ_ERR_ARG before any device work.
+ *
+ *   cwq_col_sums : acc[j] += sum_r X[r][j]                       X [n*d] fp32, acc [d] fp64
+ *   cwq_gram_acc : acc[i][j] += sum_r (A[r][i] - ctr_a[i]) (B[r][j] - ctr_b[j])
+ *                  A [n*da], B [n*db] fp32; ctr_a [da], ctr_b [db] or NULL; acc [da*db] fp64.
+ *                  With A == B, ctr_a == ctr_b only the upper tiles are computed and mirrored.
+ *   cwq_ica_g    : G = tanh(X1 W^T) [n*p] fp32, gsum[j] += sum_r (1 - G[r][j]^2) [p] fp64
+ *                  (FastICA's logcosh g and g', sklearn _fastica.py _logcosh with alpha = 1)
+ *                  X1 [n*p], W [p*p] fp32.
+ */
+int cwq_whitenfit_slab(void);
+int64_t cwq_col_sums_work_bytes(int64_t n, int32_t d);
+int64_t cwq_gram_acc_work_bytes(int64_t n, int32_t da, int32_t db);
+int64_t cwq_ica_g_work_bytes(int64_t n, int32_t p);
+int cwq_col_sums(const float* X, int64_t n, int32_t d, double* acc, void* work, void* stream);
+int cwq_gram_acc(const float* A, const float* B, int64_t n, int32_t da, int32_t db, const float* ctr_a,
+                 const float* ctr_b, double* acc, void* work, void* stream);
+int cwq_ica_g(const float* X1, int64_t n, int32_t p, const float* W, float* G, double* gsum, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

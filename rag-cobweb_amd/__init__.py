@@ -11,7 +11,7 @@ Package layout (directory ``rag-cobweb_amd/``, imported as ``rag_cobweb_amd`` vi
   wrapper.py CobwebWrapper drop-in (same API as src/cobweb/CobwebWrapper.py)
   dist.py    multi-GPU: RCCL broadcast of the index + query sharding
   harness.py batched evaluate_retrieval metrics + brute-force ground truth
-  whitening.py PCA + ICA whitening transform (fp32 MFMA)
+  whitening.py PCA + ICA, ZCA and PCA-ZCA whitening: transform and fit on the GPU (fp32 MFMA)
 """
 from . import build  # noqa: F401
 from ._lib import CwqError, lib  # noqa: F401

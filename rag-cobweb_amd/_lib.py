@@ -49,6 +49,13 @@ SIGNATURES = {
     "cwq_score_topk_host": (_c.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "cwq_categorize_host": (_c.c_int, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P]),
     "cwq_whiten": (_c.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _I32, _P, _P, _P]),
+    "cwq_whitenfit_slab": (_c.c_int, []),
+    "cwq_col_sums_work_bytes": (_I64, [_I64, _I32]),
+    "cwq_gram_acc_work_bytes": (_I64, [_I64, _I32, _I32]),
+    "cwq_ica_g_work_bytes": (_I64, [_I64, _I32]),
+    "cwq_col_sums": (_c.c_int, [_P, _I64, _I32, _P, _P, _P]),
+    "cwq_gram_acc": (_c.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
+    "cwq_ica_g": (_c.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P]),
     "cwq_fit_kl": (_c.c_int, [_P, _P, _P, _I32, _P, _c.c_float, _I32, _P, _I32, _P, _P]),
     "cwq_fit_node_op": (_c.c_int, [_I32, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "cwq_welford_groups": (_c.c_int, [_P, _I64, _I32, _P, _P, _I64, _P, _P, _P, _P]),

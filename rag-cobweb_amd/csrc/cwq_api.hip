@@ -4071,3 +4071,50 @@ extern "C" int cwq_whiten(const float* X, int64_t n, int32_t d_in, const float* 
   if (unmix) HIPCHK(launch_gemm_nt_f32(pca, n, d_pca, nullptr, unmix, d_out, nullptr, out, s));
   return CWQ_OK;
 }
+
+// ---- whitening fit: column sums, TN Gram, FastICA's G pass (cwq_whitenfit.hip) ----
+static bool wf_dim_ok(int32_t d) { return d >= 1 && d <= 1024; }
+
+extern "C" int cwq_whitenfit_slab(void) { return kWfSlab; }
+
+extern "C" int64_t cwq_col_sums_work_bytes(int64_t n, int32_t d) {
+  if (n < 0 || !wf_dim_ok(d)) return -1;
+  return ((n + kWfSlab - 1) / kWfSlab) * d * (int64_t)sizeof(double);
+}
+
+extern "C" int64_t cwq_gram_acc_work_bytes(int64_t n, int32_t da, int32_t db) {
+  if (n < 0 || !wf_dim_ok(da) || !wf_dim_ok(db)) return -1;
+  return ((n + kWfSlab - 1) / kWfSlab) * da * db * (int64_t)sizeof(float);
+}
+
+extern "C" int64_t cwq_ica_g_work_bytes(int64_t n, int32_t p) {
+  if (n < 0 || !wf_dim_ok(p)) return -1;
+  return ((n + 127) / 128) * p * (int64_t)sizeof(double);
+}
+
+extern "C" int cwq_col_sums(const float* X, int64_t n, int32_t d, double* acc, void* work, void* stream) {
+  if (n < 0 || !wf_dim_ok(d)) return fail(CWQ_ERR_ARG, "bad column-sum shape (n >= 0, d in [1, 1024])");
+  if (!X || !acc || !work) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (n == 0) return CWQ_OK;
+  HIPCHK(launch_col_sums(X, n, d, acc, (double*)work, (hipStream_t)stream));
+  return CWQ_OK;
+}
+
+extern "C" int cwq_gram_acc(const float* A, const float* B, int64_t n, int32_t da, int32_t db, const float* ctr_a,
+                            const float* ctr_b, double* acc, void* work, void* stream) {
+  if (n < 0 || !wf_dim_ok(da) || !wf_dim_ok(db))
+    return fail(CWQ_ERR_ARG, "bad Gram shape (n >= 0, da and db in [1, 1024])");
+  if (!A || !B || !acc || !work) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (n == 0) return CWQ_OK;
+  HIPCHK(launch_gram_acc(A, B, n, da, db, ctr_a, ctr_b, acc, (float*)work, (hipStream_t)stream));
+  return CWQ_OK;
+}
+
+extern "C" int cwq_ica_g(const float* X1, int64_t n, int32_t p, const float* W, float* G, double* gsum, void* work,
+                         void* stream) {
+  if (n < 0 || !wf_dim_ok(p)) return fail(CWQ_ERR_ARG, "bad ICA shape (n >= 0, p in [1, 1024])");
+  if (!X1 || !W || !G || !gsum || !work) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (n == 0) return CWQ_OK;
+  HIPCHK(launch_ica_g(X1, n, p, W, G, gsum, (double*)work, (hipStream_t)stream));
+  return CWQ_OK;
+}

@@ -965,4 +965,16 @@ hipError_t launch_ce_coef(const CeArgs& a, const RowMeta* meta, int NL_iso, floa
 hipError_t launch_gemm_nt_f32(const float* A, int64_t M, int K, const float* ctr, const float* B, int N,
                               const float* denom, float* C, hipStream_t s);
 
+// ---- whitening fit (cwq_whitenfit.hip): fixed row slabs, fp32 MFMA partials, fp64 combine ----
+constexpr int kWfSlab = 4096;   // rows per slab of the column sums and of the TN Gram
+constexpr int kWfFold = 32;     // TN Gram: LDS stages (16 rows each) per fp32 fma chain
+// acc[d] += column sums of X [n][d]; work: ceil(n / kWfSlab) * d doubles
+hipError_t launch_col_sums(const float* X, int64_t n, int d, double* acc, double* work, hipStream_t s);
+// acc[da][db] += sum_r (A[r][i] - ca[i]) (B[r][j] - cb[j]); work: ceil(n / kWfSlab) * da * db floats
+hipError_t launch_gram_acc(const float* A, const float* B, int64_t n, int da, int db, const float* ca, const float* cb,
+                           double* acc, float* work, hipStream_t s);
+// G[n][p] = tanh(X1 W^T), gsum[p] += sum_r (1 - G^2); work: ceil(n / 128) * p doubles
+hipError_t launch_ica_g(const float* X1, int64_t n, int p, const float* W, float* G, double* gsum, double* work,
+                        hipStream_t s);
+
 }  // namespace cwq
