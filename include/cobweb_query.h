@@ -394,6 +394,64 @@ int cwq_mt19937_words(uint32_t* state625, int64_t n, uint32_t* out);
 int cwq_mt19937_skip(uint32_t* state625, int64_t nwords);
 
 /*
+ * The device-resident tree between an add and the next query: the query index built
+ * straight from a cwq_fit handle, the handle grown in place, and the random() state moved
+ * on its own.  Replaces, per CobwebWrapper.add_sentences -> cobweb_predict* cycle
+ * (CobwebWrapper.py:52-89), the host passes over every node: the BFS flatten and
+ * compute_var of build_prediction_index (CobwebWrapper.py:107-203, CobwebTorchTree.py:336-342)
+ * and the export / reload of the whole tree around each insert batch.  No [n_nodes*dim]
+ * float array crosses PCIe.  All calls validate their arguments before any device work
+ * (CWQ_ERR_ARG, message in cwq_fit_last_error; cwq_index_create_from_fit also sets
+ * cwq_last_error), and are ordered on `stream`.
+ *
+ *   cwq_fit_flatten   the live tree in BFS numbering -- exactly CobwebWrapper's (root 0, a
+ *                     node's children consecutive in child-list order, levels in order;
+ *                     slots a split removed get no number) -- as device arrays owned by the
+ *                     returned object: mean [n_nodes*dim], count [n_nodes], the variances meanSq / count +
+ *                     prior_var (numpy float32 bits; prior_var for an empty node) in
+ *                     cwq_index_create_cv's compact form (var_row [n_nodes], an_nodes [n_an]
+ *                     ascending = the nodes whose dim variances are not all the same bits,
+ *                     an_var [n_an*dim]), parent [n_nodes] int64, slot_of_node [n_nodes] int32
+ *                     and node_of_sentence [n_sent] int64 from slot_of_sentence (device
+ *                     [n_sent] int32, the slot holding each sentence; -1 or a slot that is
+ *                     not in the tree: -1).  Trees of up to 64 levels below the root; deeper
+ *                     ones are CWQ_ERR_ARG.  One 8-byte readback per level.
+ *   cwq_fit_flat_info o[8] = {n_nodes, n_an, n_sent, dim, levels below the root, slots in
+ *                     use, device bytes held, 0}
+ *   cwq_fit_flat_copy device-to-device copies into the caller's arrays (NULL: skipped)
+ *   cwq_index_create_from_fit  flatten, download parent and node_of_sentence (8 B per node
+ *                     and per sentence), build the index from the device-resident mean and
+ *                     compact variances (the index of cwq_index_create_cv on the same
+ *                     arrays), free the temporaries
+ *   cwq_fit_grow      the pool and the child arena re-allocated at new_cap_nodes (> the
+ *                     capacity) device to device, slot numbers unchanged, child lists
+ *                     re-packed at max(4, 2 * length) as cwq_fit_load lays them out; control
+ *                     words, log-variance cache and random() state kept.  Answers a status-1
+ *                     return of cwq_fit_insert without export and reload.  CWQ_ERR_OOM: the new
+ *                     pool cannot be allocated; the handle is unchanged and usable
+ *   cwq_fit_set_rng / cwq_fit_get_rng   upload / download the handle's random() state (host
+ *                     [625]: random.getstate()[1]), for the one global stream that ifit and
+ *                     categorize share (CobwebTorchTree.py:243,268,285)
+ *   cwq_fit_rewind    the next cwq_fit_insert starts at row 0 of its X again (a new batch into
+ *                     the same handle)
+ *   cwq_fit_info      o[8] = {capacity, slots in use, root slot, slots removed by splits, arena
+ *                     top, arena capacity, rows done, random() draws}
+ */
+typedef struct cwq_fit_flat cwq_fit_flat;
+int cwq_fit_flatten(cwq_fit* h, const int32_t* slot_of_sentence, int64_t n_sent, void* stream, cwq_fit_flat** out);
+int cwq_fit_flat_info(const cwq_fit_flat* flat, int64_t* out8);
+int cwq_fit_flat_copy(const cwq_fit_flat* flat, float* mean, float* count, float* var_row, int64_t* an_nodes, float* an_var,
+                      int64_t* parent, int64_t* node_of_sentence, int32_t* slot_of_node, void* stream);
+int cwq_fit_flat_destroy(cwq_fit_flat* flat);
+int cwq_index_create_from_fit(cwq_fit* h, const int32_t* slot_of_sentence, int64_t n_sent, const double* level_w,
+                              int32_t n_w, void* stream, cwq_index** out);
+int cwq_fit_grow(cwq_fit* h, int32_t new_cap_nodes, void* stream);
+int cwq_fit_set_rng(cwq_fit* h, const uint32_t* state625, void* stream);
+int cwq_fit_get_rng(cwq_fit* h, uint32_t* state625, void* stream);
+int cwq_fit_rewind(cwq_fit* h, void* stream);
+int cwq_fit_info(cwq_fit* h, int64_t* out8, void* stream);
+
+/*
  * PCA + ICA whitening transform (F4).  Replaces PCAICAWhiteningModel.transform
  * (src/whitening/pca_ica.py:30-51), the embedding normalisation of the "PCA + ICA"
  * benchmark rows and of config C5:

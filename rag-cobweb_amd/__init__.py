@@ -7,6 +7,7 @@ Package layout (directory ``rag-cobweb_amd/``, imported as ``rag_cobweb_amd`` vi
   index.py   CobwebIndex: the device-resident flattened tree + query calls
   tree.py    host concept tree, reference JSON format, BFS flattening
   fit.py     incremental fit (ifit) with GPU category-utility scoring
+  resident.py ResidentTree: the tree kept on the GPU between adds and queries (resident=True)
   synth.py   synthetic flat / two-level trees for the 1M-10M configurations
   wrapper.py CobwebWrapper drop-in (same API as src/cobweb/CobwebWrapper.py)
   dist.py    multi-GPU: RCCL broadcast of the index + query sharding
@@ -21,7 +22,7 @@ from .tree import PRIOR_VAR, CobwebTree, Node  # noqa: F401
 def __getattr__(name):
     # torch-dependent modules load lazily so that `build()` works without touching the GPU
     import importlib
-    if name in ("index", "synth", "wrapper", "fit", "dist", "harness", "whitening"):
+    if name in ("index", "synth", "wrapper", "fit", "dist", "harness", "whitening", "resident"):
         return importlib.import_module(f".{name}", __name__)
     if name == "CobwebWrapper":
         return importlib.import_module(".wrapper", __name__).CobwebWrapper

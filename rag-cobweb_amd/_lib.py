@@ -65,6 +65,16 @@ SIGNATURES = {
     "cwq_fit_insert": (_c.c_int, [_P, _P, _I64, _P, _P, _P]),
     "cwq_fit_export": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cwq_fit_last_error": (_c.c_char_p, []),
+    "cwq_fit_flatten": (_c.c_int, [_P, _P, _I64, _P, _c.POINTER(_P)]),
+    "cwq_fit_flat_info": (_c.c_int, [_P, _P]),
+    "cwq_fit_flat_copy": (_c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cwq_fit_flat_destroy": (_c.c_int, [_P]),
+    "cwq_index_create_from_fit": (_c.c_int, [_P, _P, _I64, _P, _I32, _P, _c.POINTER(_P)]),
+    "cwq_fit_grow": (_c.c_int, [_P, _I32, _P]),
+    "cwq_fit_set_rng": (_c.c_int, [_P, _P, _P]),
+    "cwq_fit_get_rng": (_c.c_int, [_P, _P, _P]),
+    "cwq_fit_rewind": (_c.c_int, [_P, _P]),
+    "cwq_fit_info": (_c.c_int, [_P, _P, _P]),
     "cwq_mt19937_draw": (_c.c_int, [_P, _I64, _P]),
     "cwq_mt19937_words": (_c.c_int, [_P, _I64, _P]),
     "cwq_mt19937_skip": (_c.c_int, [_P, _I64]),

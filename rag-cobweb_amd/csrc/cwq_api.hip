@@ -1355,6 +1355,24 @@ extern "C" int cwq_index_create_cv(int device, int64_t n_nodes, int32_t dim, con
   return rc;
 }
 
+// cwq_index_create_from_fit (cwq_fitindex.hip): mean and the compact variances (VarSrc with
+// its an_map) already on the device; parent / node_of_sentence on the host.  Errors go to
+// cwq_last_error (msg_out: the message, for the caller's own error slot).
+namespace cwq {
+int index_create_device(int device, int64_t n_nodes, int32_t dim, const float* mean, const VarSrc& var,
+                        const int64_t* parent, const int64_t* node_of_sentence, int64_t n_sent,
+                        const double* level_w, int32_t n_w, hipStream_t s, cwq_index** out, const char** msg_out) {
+  int rc = create_args_ok(n_nodes, dim, mean, parent, node_of_sentence, n_sent, out);
+  if (!rc) {
+    DevGuard dg(device);
+    rc = index_create_impl(device, n_nodes, dim, mean, var, parent, node_of_sentence, n_sent, level_w, n_w, s, out);
+  }
+  if (msg_out) *msg_out = g_err.c_str();
+  return rc;
+}
+int index_fail(int code, const char* msg) { return fail(code, msg); }
+}  // namespace cwq
+
 extern "C" int cwq_index_destroy(cwq_index* idx) {
   if (!idx) return CWQ_OK;
   DevGuard dg(idx->device);

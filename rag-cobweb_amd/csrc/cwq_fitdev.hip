@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/cobweb_query.h"
+#include "cwq_internal.h"
 #include "cwq_refmath.h"
 
 namespace cwq {
@@ -48,7 +49,6 @@ namespace cwq {
 // ---------------------------------------------------------------------------
 // MT19937 with Python's random.random() (genrand_res53): state = 624 words + index
 // ---------------------------------------------------------------------------
-constexpr int kMtN = 624, kMtM = 397;
 __host__ __device__ inline uint32_t mt_u32(uint32_t* mt, int& idx) {
   if (idx >= kMtN) {
     int kk = 0;
@@ -125,34 +125,8 @@ inline void mt_twist_chains_host(uint32_t* mt) {
 }
 
 // ---------------------------------------------------------------------------
-// Device tree
+// Device tree (struct FitDev: cwq_internal.h)
 // ---------------------------------------------------------------------------
-struct FitDev {
-  int D;
-  float pv;
-  int cap;                      // node slots
-  float *count, *mean, *meanSq; // [cap], [cap][D]
-  float* lvar;                  // [cap][D] ref_logf(meanSq / count + pv): a node's log-variances, kept
-                                // current by fd_increment / fd_combine and set for every loaded node
-  int *parent, *ccnt, *ccap;    // [cap]
-  int64_t* coff;                // [cap] child slab offset in the arena
-  int* arena;
-  int64_t arena_cap;
-  int* ctrl;                    // [0] used [2] root [3] status [4] mt index
-  int64_t* ctrl64;              // [0] arena_top [1] rows done [2] randoms drawn
-  uint32_t* mt;                 // [624]
-  float *kres, *gain, *tall, *tins, *ncv;   // per-level scratch [cap]
-  int* jobs;                    // [cap] split job nodes
-  // the chip-wide KL pass (fork / join between the master workgroup and its helpers)
-  struct FdJob* job;
-  float* pvec;                  // [3][D] the job's reference vectors (mean, var, log var)
-  uint32_t* rnd;                // [2*cap + 8] a level's tempered MT outputs (the sort's draws)
-  int fork_min;                 // fork a level's KL pass when it has >= fork_min children
-  uint64_t spin_ticks;          // bound of every spin (100 MHz steady counter ticks)
-  int* dbg;                     // [16] progress words (read back by the host on FD_HANG)
-  int prof;                     // CWQ_FIT_PROFILE: forked levels' phase ticks into dbg[8..13], count dbg[14] ("all": every level)
-};
-
 // 512 threads (8 waves): up to 256 VGPRs per lane -- the torch-order KL sums
 // (cwq_refmath.h) spilled at 1024 threads' 128 (the kernel takes ~170, so one workgroup per CU)
 constexpr int kFdThreads = 512;
@@ -1342,37 +1316,24 @@ __global__ void fd_lvar_kernel(const FitDev f, int n) {
 
 using namespace cwq;
 
-struct cwq_fit {
-  int device = 0;
-  FitDev f{};
-  std::vector<void*> allocs;
-  void* zero = nullptr;
-};
-
 static thread_local std::string g_fit_err;
 static int fit_fail(int code, const std::string& m) {
   g_fit_err = m;
   return code;
 }
+int cwq::fit_fail(int code, const char* msg) { return ::fit_fail(code, std::string(msg)); }
 
 extern "C" const char* cwq_fit_last_error(void) { return g_fit_err.c_str(); }
 
-extern "C" int cwq_fit_create(int device, int32_t dim, float prior_var, int32_t cap_nodes, cwq_fit** out) {
-  if (!out || dim <= 0 || dim > kFdMaxD || cap_nodes <= 0) return fit_fail(CWQ_ERR_ARG, "bad cwq_fit_create arguments");
-  *out = nullptr;
-  if (hipSetDevice(device) != hipSuccess) return fit_fail(CWQ_ERR_HIP, "hipSetDevice failed");
-  std::unique_ptr<cwq_fit> h(new cwq_fit());
-  h->device = device;
-  FitDev& f = h->f;
-  f.D = dim;
-  f.pv = prior_var;
+bool cwq::fit_alloc(FitDev& f, int cap_nodes, std::vector<void*>& allocs) {
+  const int dim = f.D;
   f.cap = cap_nodes;
   // child-list arena: a load uses <= 6 entries per node (lists at twice their length, >= 4),
   // inserts stop for room at half of it, which keeps room for the largest list to double
   f.arena_cap = (int64_t)16 * cap_nodes + 4096;
   auto al = [&](void** p, size_t b) -> bool {
     if (hipMalloc(p, b < 256 ? 256 : b) != hipSuccess) return false;
-    h->allocs.push_back(*p);
+    allocs.push_back(*p);
     return true;
   };
   const size_t C = (size_t)cap_nodes;
@@ -1387,7 +1348,24 @@ extern "C" int cwq_fit_create(int device, int32_t dim, float prior_var, int32_t 
             al((void**)&f.pvec, (size_t)3 * dim * 4) && al((void**)&f.rnd, (2 * C + 8) * 4) &&
             al((void**)&f.dbg, 64);
   if (!ok) {
-    for (void* p : h->allocs) (void)hipFree(p);
+    for (void* p : allocs) (void)hipFree(p);
+    allocs.clear();
+  }
+  return ok;
+}
+
+extern "C" int cwq_fit_create(int device, int32_t dim, float prior_var, int32_t cap_nodes, cwq_fit** out) {
+  if (!out || dim <= 0 || dim > kFdMaxD || cap_nodes <= 0) return fit_fail(CWQ_ERR_ARG, "bad cwq_fit_create arguments");
+  *out = nullptr;
+  if (hipSetDevice(device) != hipSuccess) return fit_fail(CWQ_ERR_HIP, "hipSetDevice failed");
+  std::unique_ptr<cwq_fit> h(new cwq_fit());
+  h->device = device;
+  FitDev& f = h->f;
+  f.D = dim;
+  f.pv = prior_var;
+  f.cap = cap_nodes;
+  const bool ok = fit_alloc(f, cap_nodes, h->allocs);
+  if (!ok) {
     return fit_fail(CWQ_ERR_OOM, "cwq_fit_create: device allocation failed");
   }
   *out = h.release();

@@ -977,4 +977,54 @@ hipError_t launch_gram_acc(const float* A, const float* B, int64_t n, int da, in
 hipError_t launch_ica_g(const float* X1, int64_t n, int p, const float* W, float* G, double* gsum, double* work,
                         hipStream_t s);
 
+// ---- device-resident fit (cwq_fitdev.hip; read by cwq_fitindex.hip) ----
+constexpr int kMtN = 624, kMtM = 397;   // MT19937: state = 624 words + index
+// The device tree of a cwq_fit handle.
+struct FitDev {
+  int D;
+  float pv;
+  int cap;                      // node slots
+  float *count, *mean, *meanSq; // [cap], [cap][D]
+  float* lvar;                  // [cap][D] ref_logf(meanSq / count + pv): a node's log-variances, kept
+                                // current by fd_increment / fd_combine and set for every loaded node
+  int *parent, *ccnt, *ccap;    // [cap]
+  int64_t* coff;                // [cap] child slab offset in the arena
+  int* arena;
+  int64_t arena_cap;
+  int* ctrl;                    // [0] used [2] root [3] status [4] mt index
+  int64_t* ctrl64;              // [0] arena_top [1] rows done [2] randoms drawn
+  uint32_t* mt;                 // [624]
+  float *kres, *gain, *tall, *tins, *ncv;   // per-level scratch [cap]
+  int* jobs;                    // [cap] split job nodes
+  // the chip-wide KL pass (fork / join between the master workgroup and its helpers)
+  struct FdJob* job;
+  float* pvec;                  // [3][D] the job's reference vectors (mean, var, log var)
+  uint32_t* rnd;                // [2*cap + 8] a level's tempered MT outputs (the sort's draws)
+  int fork_min;                 // fork a level's KL pass when it has >= fork_min children
+  uint64_t spin_ticks;          // bound of every spin (100 MHz steady counter ticks)
+  int* dbg;                     // [16] progress words (read back by the host on FD_HANG)
+  int prof;                     // CWQ_FIT_PROFILE: forked levels' phase ticks into dbg[8..13], count dbg[14] ("all": every level)
+};
+int fit_fail(int code, const char* msg);   // sets cwq_fit_last_error's message; returns code
+
+}  // namespace cwq
+
+#include <vector>
+struct cwq_index;
+struct cwq_fit {
+  int device = 0;
+  cwq::FitDev f{};
+  std::vector<void*> allocs;
+  void* zero = nullptr;
+};
+namespace cwq {
+// Allocate the device arrays of a tree of cap_nodes slots (f.D, f.pv set by the caller) into
+// f, every pointer recorded in allocs; false (nothing left allocated) when one fails.
+bool fit_alloc(FitDev& f, int cap_nodes, std::vector<void*>& allocs);
+// index_create_impl (cwq_api.hip) for inputs already on the device: mean and the compact
+// variances (VarSrc with its an_map); parent / node_of_sentence on the host
+int index_create_device(int device, int64_t n_nodes, int32_t dim, const float* mean, const VarSrc& var,
+                        const int64_t* parent, const int64_t* node_of_sentence, int64_t n_sent,
+                        const double* level_w, int32_t n_w, hipStream_t s, ::cwq_index** out, const char** msg_out);
+int index_fail(int code, const char* msg);   // sets cwq_last_error's message; returns code
 }  // namespace cwq

@@ -139,6 +139,30 @@ class CobwebIndex:
         self._h = h
         self.info = self._info()
 
+    @classmethod
+    def from_fit(cls, fit, slot_of_sentence, level_weights=None, device=None):
+        """The index of a device-resident tree (a cwq_fit handle, resident.ResidentTree)
+        built on the device (cwq_index_create_from_fit): `slot_of_sentence` [n_sent] int32 on
+        the device holds each sentence's slot (-1: not in the tree).  Same index as
+        CobwebIndex(mean, var, parent, node_of_sentence) of the flattened tree; only the
+        integer structure passes through the host."""
+        self = cls.__new__(cls)
+        self.device = _dev(device)
+        L = self._L = lib()
+        sos = torch.as_tensor(slot_of_sentence, dtype=torch.int32).to(self.device).contiguous()
+        w = np.ascontiguousarray(np.asarray(
+            DEFAULT_LEVEL_WEIGHTS if level_weights is None else level_weights, dtype=np.float64))
+        self.level_weights = [float(x) for x in w]
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(L.cwq_index_create_from_fit(fit, _ptr(sos) if sos.numel() else None, int(sos.numel()),
+                                              w.ctypes.data_as(ctypes.c_void_p), w.size, _stream(self.device),
+                                              ctypes.byref(h)))
+        self._h = h
+        self.info = self._info()
+        self.n_nodes, self.dim, self.n_sent = self.info["n_nodes"], self.info["dim"], self.info["n_sent"]
+        return self
+
     def _info(self):
         out = np.zeros(8, np.int64)
         check(self._L.cwq_index_info(self._h, out.ctypes.data_as(ctypes.c_void_p)))

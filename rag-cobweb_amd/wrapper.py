@@ -58,8 +58,16 @@ def advance_random(n, rng=random):
 
 
 class CobwebWrapper:
-    def __init__(self, corpus=None, corpus_embeddings=None, encode_func=lambda x: x, device=None):
-        """CobwebWrapper.py:13-50."""
+    def __new__(cls, *args, resident=False, **kwargs):
+        # resident=True: the same interface over a tree that stays on the GPU between adds
+        # and queries (resident.ResidentCobwebWrapper); the default is this class itself
+        if resident and cls is CobwebWrapper:
+            from .resident import ResidentCobwebWrapper
+            cls = ResidentCobwebWrapper
+        return object.__new__(cls)
+
+    def __init__(self, corpus=None, corpus_embeddings=None, encode_func=lambda x: x, device=None, resident=False):
+        """CobwebWrapper.py:13-50.  resident: see __new__ (it chose the class)."""
         self.encode_func = encode_func
         self.sentences = []
         self.sentence_to_node = {}
@@ -380,7 +388,7 @@ class CobwebWrapper:
         return json.dumps(state, indent=2)
 
     @staticmethod
-    def load_json(json_data, encode_func=lambda x: x, device=None):
+    def load_json(json_data, encode_func=lambda x: x, device=None, resident=False):
         """CobwebWrapper.py:500-555, without its two bugs (identity encoder has no
         .shape; list sentence ids are unhashable): the tree shape comes from the
         JSON and every sentence id of a node maps to that node."""
@@ -396,7 +404,7 @@ class CobwebWrapper:
             for s in n.sentence_id or []:
                 w.sentence_to_node[s] = n
             stack.extend(n.children)
-        return w
+        return _as_resident(w) if resident else w
 
     def save_binary(self, path):
         """Binary counterpart of dump_json (F2): the tree's BFS arrays plus the
@@ -406,7 +414,7 @@ class CobwebWrapper:
                                            "max_init_search": np.asarray([self.max_init_search], np.int64)})
 
     @staticmethod
-    def load_binary(path, encode_func=lambda x: x, device=None):
+    def load_binary(path, encode_func=lambda x: x, device=None, resident=False):
         head, a = CobwebTree.read_binary(path)
         sentences = json.loads(bytes(a.pop("sentences")).decode()) if "sentences" in a else []
         mis = int(a.pop("max_init_search")[0]) if "max_init_search" in a else MAX_INIT_SEARCH
@@ -417,11 +425,13 @@ class CobwebWrapper:
         w = CobwebWrapper.from_tree(t, sentences, device=device)
         w.encode_func = encode_func
         w.max_init_search = mis
-        return w
+        return _as_resident(w) if resident else w
 
     @classmethod
-    def from_tree(cls, tree, sentences, device=None):
+    def from_tree(cls, tree, sentences, device=None, resident=False):
         """Wrap an existing CobwebTree (e.g. CobwebTree.from_arrays / from_json)."""
+        if resident:
+            return _as_resident(CobwebWrapper.from_tree(tree, sentences, device=device))
         w = cls(device=device)
         w.tree = tree
         w.sentences = list(sentences)
@@ -450,6 +460,12 @@ class CobwebWrapper:
 
     def __len__(self):
         return len(self.sentences)
+
+
+def _as_resident(w):
+    """The resident counterpart of a default wrapper that was just loaded from a host tree."""
+    from .resident import ResidentCobwebWrapper
+    return ResidentCobwebWrapper._adopt(w)
 
 
 class _NodeSentences:
