@@ -76,7 +76,10 @@ def test_one_leaf_tree(gpu):
                                       (20000, 17, 7, 10), (18000, 100, 64, 33), (18000, 100, 65, 1)])
 def test_odd_dimensions(gpu, N, D, nq, k):
     """D not a multiple of 16/32: zero padding of the fp32 scan layout, the bf16 operand
-    (whole 64-deep stages) and the stream filter's fragments must not change a key."""
+    (whole 64-deep stages) and the stream filter's fragments must not change a key.
+    These trees are flat (one internal node, isotropic count-1 leaves) and go through Fast
+    only; ragged ifit trees at odd dimensions through every query path, against fp64, are in
+    tests/test_gpu_ragged_odd_dim.py."""
     X = gpu.synth.synthetic_corpus(N, D, seed=N + D)
     ix = flat_index(gpu, X)
     Q, _ = gpu.synth.synthetic_queries(X, nq, seed=D)
