@@ -198,6 +198,36 @@ int cwq_rank_ce(cwq_index* idx, const float* q, int64_t nq, const int64_t* targe
                 float* loss, float* grad_q, float* target_score, int64_t* rank, void* stream);
 
 /*
+ * The three calls above under call-time level weights, with the gradient with respect to them.
+ * The Fast score is linear in the level weights (score = (1/L) sum_depth w[depth] lp'(node));
+ * an index bakes them in at creation, and these calls evaluate it under another vector
+ * without a rebuild and return d/dw, so a schedule can be swept or learned against a fixed
+ * index and written back once (a new index with the learned weights).
+ *   level_w  device [n_w] fp32 on the index's device, read by the kernels only (no host read,
+ *            no sync); a depth >= n_w weighs 1.0, as at index creation.  Any finite value of
+ *            either sign; non-finite weights propagate as in torch.  NULL: the index's own
+ *            weights -- the outputs are then exactly those of the calls above.
+ *   n_w      0 <= n_w <= 64
+ *   grad_w   device [nq*n_w] fp32 or NULL: cwq_rank_scores_backward_w: d(sum grad_out *
+ *            scores[q])/dw per query; cwq_rank_ce_w: d loss[q]/dw.  Per query, not reduced;
+ *            columns of levels deeper than the tree are 0; an invalid target gives a zero row.
+ *            fp64 accumulation in a fixed order over fixed row ranges, no atomics: identical
+ *            from run to run, for a query alone, in any batch and under workspace chunking.
+ *   grad_q   as above; may be NULL in cwq_rank_scores_backward_w when grad_w is not.
+ * With level_w given, the forward outputs and grad_q are bit for bit those of an index created
+ * with these weights (as doubles).  The index is not modified.  CWQ_ERR_ARG before any device
+ * work for n_w outside [0, 64] or a NULL required pointer.  Only these exact paths take
+ * call-time weights: retrieval (cwq_score_topk and the filters) reads the baked ones.
+ */
+int cwq_rank_scores_w(cwq_index* idx, const float* q, int64_t nq, const float* level_w, int32_t n_w, float* out,
+                      void* stream);
+int cwq_rank_scores_backward_w(cwq_index* idx, const float* q, int64_t nq, const float* grad_out,
+                               const float* level_w, int32_t n_w, float* grad_q, float* grad_w, void* stream);
+int cwq_rank_ce_w(cwq_index* idx, const float* q, int64_t nq, const int64_t* target, float temperature,
+                  const float* level_w, int32_t n_w, float* loss, float* grad_q, float* grad_w, float* target_score,
+                  int64_t* rank, void* stream);
+
+/*
  * Per-node Gaussian log-likelihood for every node in BFS order.
  *   full = 0: lp'(n) as CobwebWrapper.py:232-236 (no 2*pi term)
  *   full = 1: CobwebTorchNode.log_prob (CobwebTorchNode.py:100-104, with 2*pi)

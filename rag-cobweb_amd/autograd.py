@@ -6,6 +6,11 @@ Forward is `CobwebIndex.rank_scores` (cwq_rank_scores), backward is
 `CobwebIndex.rank_scores_backward` (cwq_rank_scores_backward): both run in
 libcwq on torch's current stream.  The backward needs only the queries, the upstream
 gradient and the index, so nothing of the forward is stored.
+
+Both functions also take the level weights as a differentiable input (`level_weights`,
+cwq_rank_scores_w / cwq_rank_scores_backward_w / cwq_rank_ce_w): the scores
+are evaluated under that vector instead of the weights baked into the index, and its .grad is
+the per-query weight gradient summed over the batch.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -28,57 +33,87 @@ class _Pin:
 
 
 class RankScores(torch.autograd.Function):
-    """scores = index.rank_scores(q) for q float32 [nq, dim] on the index device."""
+    """scores = index.rank_scores(q, w) for q float32 [nq, dim] and w (None, or float32 [n_w])
+    on the index device."""
 
     @staticmethod
-    def forward(ctx, q, index):
+    def forward(ctx, q, index, w=None):
         ctx.index = index
         ctx.pin = _Pin(index)
-        ctx.save_for_backward(q)
-        return index.rank_scores(q.detach())
+        ctx.has_w = w is not None
+        ctx.save_for_backward(*((q, w) if ctx.has_w else (q,)))
+        return index.rank_scores(q.detach()) if w is None else index.rank_scores(q.detach(), w.detach())
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        (q,) = ctx.saved_tensors
-        return ctx.index.rank_scores_backward(q, grad_out), None
+        q = ctx.saved_tensors[0]
+        w = ctx.saved_tensors[1] if ctx.has_w else None
+        need_q = ctx.needs_input_grad[0]
+        need_w = ctx.has_w and ctx.needs_input_grad[2]
+        if not ctx.has_w:
+            return ctx.index.rank_scores_backward(q, grad_out), None, None
+        if not need_w:
+            return ctx.index.rank_scores_backward(q, grad_out, w), None, None
+        gq, gw = ctx.index.rank_scores_backward(q, grad_out, w, weight_grad=True, query_grad=need_q)
+        return gq, None, gw.sum(0)
 
 
 class RankCE(torch.autograd.Function):
-    """(loss [nq], target_score [nq], rank [nq]) = index.rank_ce(q, target, T) for q float32
+    """(loss [nq], target_score [nq], rank [nq]) = index.rank_ce(q, target, T, w) for q float32
     [nq, dim] on the index device (cwq_rank_ce).  The forward computes
-    d loss / d q with the loss when q requires grad and saves it: the backward is a torch
-    multiply, no library call, so the index needs no pin."""
+    d loss / d q (and d loss / d w per query) with the loss where they are needed and saves
+    them: the backward is torch arithmetic, no library call, so the index needs no pin."""
 
     @staticmethod
-    def forward(ctx, q, index, target, temperature, need):
-        loss, gq, tscore, rank = index.rank_ce(q.detach(), target, temperature, grad=need)
-        if need:
-            ctx.save_for_backward(gq)
+    def forward(ctx, q, index, target, temperature, need, w=None, need_w=False):
+        if w is None:
+            loss, gq, tscore, rank, *gw = index.rank_ce(q.detach(), target, temperature, grad=need)
+        else:
+            loss, gq, tscore, rank, *gw = index.rank_ce(q.detach(), target, temperature, grad=need,
+                                                        level_weights=w.detach(), weight_grad=need_w)
+        ctx.need, ctx.need_w = need, need_w
+        ctx.save_for_backward(*([gq] if need else []), *gw)
         ctx.mark_non_differentiable(tscore, rank)
         return loss, tscore, rank
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_loss, _gs, _gr):
-        (gq,) = ctx.saved_tensors
-        return gq * grad_loss[:, None], None, None, None, None
+        saved = list(ctx.saved_tensors)
+        gq = saved.pop(0) * grad_loss[:, None] if ctx.need else None
+        gw = (saved.pop(0) * grad_loss[:, None]).sum(0) if ctx.need_w else None
+        return gq, None, None, None, None, gw, None
 
 
-def rank_ce_autograd(index, q, target, temperature=1.0):
+def _weights(index, w):
+    """The level weights on the index device as float32 [n_w], by torch ops (a CPU or float64
+    parameter gets its .grad on its own device and dtype)."""
+    if w is None:
+        return None
+    w = torch.as_tensor(w)
+    if w.dim() != 1 or w.shape[0] > 64:
+        raise ValueError("level_weights must be a vector of at most 64 values")
+    return w.to(index.device, torch.float32).contiguous()
+
+
+def rank_ce_autograd(index, q, target, temperature=1.0, level_weights=None):
     """Differentiable per-query loss of index.rank_ce, with the target's score and rank: the
     device move, the cast and the reshape in front are torch ops, as in rank_scores_autograd.
-    Under torch.no_grad(), or for a q that does not require grad, no gradient pass runs."""
+    Under torch.no_grad(), or for inputs that do not require grad, no gradient pass runs."""
     if q.dim() == 1:
         q = q[None, :]
     if q.dim() != 2 or q.shape[1] != index.dim:
         raise ValueError(f"queries must be [nq, {index.dim}]")
     q = q.to(index.device, torch.float32).contiguous()
+    w = _weights(index, level_weights)
     # decided here: grad mode is always off inside a Function's forward
-    return RankCE.apply(q, index, target, temperature, bool(q.requires_grad and torch.is_grad_enabled()))
+    on = torch.is_grad_enabled()
+    need = bool(q.requires_grad and on)
+    return RankCE.apply(q, index, target, temperature, need, w, bool(w is not None and w.requires_grad and on))
 
 
-def rank_scores_autograd(index, q):
+def rank_scores_autograd(index, q, level_weights=None):
     """Differentiable index.rank_scores(q): the move to the index device, the cast and the
     [dim] -> [1, dim] reshape are torch ops, so a CPU leaf gets its .grad on the CPU."""
     if q.dim() == 1:
@@ -86,4 +121,5 @@ def rank_scores_autograd(index, q):
     if q.dim() != 2 or q.shape[1] != index.dim:
         raise ValueError(f"queries must be [nq, {index.dim}]")
     q = q.to(index.device, torch.float32).contiguous()
-    return RankScores.apply(q, index)
+    w = _weights(index, level_weights)
+    return RankScores.apply(q, index, w)

@@ -91,6 +91,7 @@ struct cwq_index {
   float *int_A = nullptr, *int_B = nullptr, *iso_M = nullptr, *an_A = nullptr, *an_B = nullptr;
   RowMeta* row_meta = nullptr;
   int *row_par = nullptr, *row_flags = nullptr, *row_bfs = nullptr;
+  int *row_depth = nullptr, *int_depth = nullptr;   // depth of each leaf-class row / internal node (call-time level weights)
   float* logdet_row = nullptr;
   float *logdet_int = nullptr, *w_int = nullptr;
   int *par_int = nullptr, *int_child_begin = nullptr, *int_child_end = nullptr, *int_nchild = nullptr;
@@ -1202,6 +1203,12 @@ int index_create_impl(int device, int64_t n_nodes, int32_t dim, const float* mea
   if ((rc = ix->upload(&ix->row_par, row_par, s))) return rc;
   if ((rc = ix->upload(&ix->row_flags, row_flags, s))) return rc;
   if ((rc = ix->upload(&ix->row_bfs, row_bfs, s))) return rc;
+  {
+    std::vector<int> rdep(ix->NL), idep(ix->NI);
+    for (int r = 0; r < ix->NL; ++r) rdep[r] = depth[rows[r]];
+    for (int i = 0; i < ix->NI; ++i) idep[i] = depth[int_nodes[i]];
+    if ((rc = ix->upload(&ix->row_depth, rdep, s)) || (rc = ix->upload(&ix->int_depth, idep, s))) return rc;
+  }
   if ((rc = ix->upload(&ix->par_int, par_int, s))) return rc;
   if ((rc = ix->upload(&ix->w_int, w_int, s))) return rc;
   if ((rc = ix->upload(&ix->int_child_begin, cb, s))) return rc;
@@ -1451,6 +1458,9 @@ struct Chunk {
   double* gsh = nullptr;
   float* Tseed = nullptr;   // group pruning's seed threshold [nq] (a lower bound of tau_K), or none
   int grp_done = -1;   // the group tables run_internal's fused pass wrote: -1 none, 0 Fast, 1 + categorize
+  // call-time level weights (cwq_lweight.hip): the exact passes read these instead of the index's
+  const float* w_int = nullptr;    // [NI]
+  const RowMeta* meta = nullptr;   // [NL]
 };
 
 // The group-centred rows' prefix tables of a chunk (after the exact internal pass wrote
@@ -1607,7 +1617,7 @@ ScanArgs base_args(const cwq_index* ix, const Chunk& c) {
   memset(&a, 0, sizeof(a));
   a.DP = ix->DP;
   a.nq = c.nq;
-  a.meta = ix->row_meta;
+  a.meta = c.meta ? c.meta : ix->row_meta;
   a.par = ix->row_par;
   a.flags = ix->row_flags;
   a.P = c.P ? c.P : ix->dummy;   // query-major: the scans run with the exact pass's P (never after pT bounds)
@@ -1626,12 +1636,13 @@ ScanArgs base_args(const cwq_index* ix, const Chunk& c) {
 constexpr int kChainMaxQ = 64, kChainMaxDepth = 16;
 int internal_prefixes(cwq_index* ix, Chunk& c, hipStream_t s, float* BF, float* LPF, float dfull, const float* q,
                       int grp_cat) {
+  const float* w_int = c.w_int ? c.w_int : ix->w_int;
   const char* fe = getenv("CWQ_INT_FINISH");
   const bool fin = ix->levels.size() > 1 && c.nq <= kChainMaxQ && ix->max_depth <= kChainMaxDepth &&
                    !(fe && *fe && atoi(fe) == 0);
   if (!fin) {
     for (auto& lv : ix->levels)
-      HIPCHK(launch_prefix_level(c.S_int, ix->NI, c.nq, lv.first, lv.second, ix->par_int, ix->w_int, ix->logdet_int,
+      HIPCHK(launch_prefix_level(c.S_int, ix->NI, c.nq, lv.first, lv.second, ix->par_int, w_int, ix->logdet_int,
                                  dfull, c.P, BF, LPF, s));
     return CWQ_OK;
   }
@@ -1644,7 +1655,7 @@ int internal_prefixes(cwq_index* ix, Chunk& c, hipStream_t s, float* BF, float* 
   f.lv0 = ix->d_lv;
   f.nlev = (int)ix->levels.size();
   f.par_int = ix->par_int;
-  f.w_int = ix->w_int;
+  f.w_int = w_int;
   f.logdet_int = ix->logdet_int;
   f.dfull = dfull;
   f.P = c.P;
@@ -1875,7 +1886,7 @@ int run_leaf_scan(cwq_index* ix, const Chunk& c, int epi, bool cat, int kl, floa
     a.rows_per_slab = rps[i];
     a.n_qblocks = nqb;
     a.seg_base = segs[i].base;
-    a.meta = ix->row_meta + segs[i].base;
+    a.meta = (c.meta ? c.meta : ix->row_meta) + segs[i].base;
     a.par = ix->row_par + segs[i].base;
     a.flags = ix->row_flags + segs[i].base;
     a.dconst = dconst;
@@ -2971,8 +2982,53 @@ extern "C" int cwq_last_timing(cwq_index* ix, float* out) {
   return CWQ_OK;
 }
 
+namespace {
+
+// Call-time level weights (cwq_lweight.hip): the chunk's RowMeta' / w_int' in the workspace,
+// read by the exact passes and the backward's coefficient kernels instead of the index's.
+size_t lw_operand_bytes(const cwq_index* ix, const float* level_w) {
+  return level_w ? (size_t)std::max(ix->NL, 1) * sizeof(RowMeta) + (size_t)std::max(ix->NI, 1) * 4 + 2 * 256 : 0;
+}
+int lw_operands(const cwq_index* ix, Bump& b, const float* level_w, int n_w, const RowMeta** meta, const float** w_int,
+                hipStream_t s) {
+  *meta = ix->row_meta;
+  *w_int = ix->w_int;
+  if (!level_w) return CWQ_OK;
+  RowMeta* m = b.take<RowMeta>(std::max(ix->NL, 1));
+  float* w = b.take<float>(std::max(ix->NI, 1));
+  HIPCHK(launch_lw_operands(level_w, n_w, ix->row_meta, ix->row_depth, ix->NL, ix->int_depth, ix->NI, m, w, s));
+  *meta = m;
+  *w_int = w;
+  return CWQ_OK;
+}
+int lw_check(const float* level_w, int32_t n_w) {
+  (void)level_w;
+  if (n_w < 0 || n_w > kLwMaxLevels) return fail(CWQ_ERR_ARG, "n_w must be in [0, 64]");
+  return CWQ_OK;
+}
+
+int rank_scores_impl(cwq_index* ix, const float* q, int64_t nq, const float* level_w, int n_w, float* out,
+                     void* stream);
+
+}  // namespace
+
 extern "C" int cwq_rank_scores(cwq_index* ix, const float* q, int64_t nq, float* out, void* stream) {
   if (!ix || (!q && nq > 0) || (!out && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
+  return rank_scores_impl(ix, q, nq, nullptr, 0, out, stream);
+}
+
+extern "C" int cwq_rank_scores_w(cwq_index* ix, const float* q, int64_t nq, const float* level_w, int32_t n_w,
+                                 float* out, void* stream) {
+  if (!ix || !q || !out) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
+  if (int rc = lw_check(level_w, n_w)) return rc;
+  return rank_scores_impl(ix, q, nq, level_w, n_w, out, stream);
+}
+
+namespace {
+
+int rank_scores_impl(cwq_index* ix, const float* q, int64_t nq, const float* level_w, int n_w, float* out,
+                     void* stream) {
   if (nq == 0) return CWQ_OK;
   std::lock_guard<std::mutex> lk(ix->mu);
   DevGuard dg(ix->device);
@@ -2985,11 +3041,14 @@ extern "C" int cwq_rank_scores(cwq_index* ix, const float* q, int64_t nq, float*
   for (int64_t q0 = 0; q0 < nq; q0 += cq) {
     const int nqc = (int)std::min(cq, nq - q0);
     const int64_t nq_pad = round_up(nqc, kQPad);
-    if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(ix->NL, 1) * 4 + 8 * 256))) return rc;
+    if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(ix->NL, 1) * 4 + 8 * 256 +
+                          lw_operand_bytes(ix, level_w))))
+      return rc;
     Bump b(ix->ws, ix->ws_size);
     Chunk c;
     carve_chunk(ix, b, c, nqc, false);
     float* rowkey = b.take<float>((size_t)nq_pad * std::max(ix->NL, 1));
+    if ((rc = lw_operands(ix, b, level_w, n_w, &c.meta, &c.w_int, s))) return rc;
     HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
     if ((rc = run_internal(ix, c, s, false))) return rc;
     if ((rc = run_leaf_scan(ix, c, EPI_KEY, false, 16, 0.f, rowkey, ix->NL, nullptr, nullptr, nullptr, 1, nullptr, s)))
@@ -2999,7 +3058,6 @@ extern "C" int cwq_rank_scores(cwq_index* ix, const float* q, int64_t nq, float*
   return CWQ_OK;
 }
 
-namespace {
 
 // The backward's launch plan: slabs, leaf-sum pieces, threads per node and workspace bytes per
 // query -- functions of the index alone (a query's gradient is the same in any batch).
@@ -3109,47 +3167,43 @@ int grad_streams(const cwq_index* ix, const GradPlan& gp, const GradCoefArgs& ca
   return CWQ_OK;
 }
 
-}  // namespace
 
-// Backward of cwq_rank_scores (cwq_grad.hip): the coefficient pass, the streaming reduction
-// over the three row classes, the slab sum.  Needs q, grad_out and the index only.
-extern "C" int cwq_rank_scores_backward(cwq_index* ix, const float* q, int64_t nq, const float* grad_out,
-                                        float* grad_q, void* stream) {
-  if (!ix || !q || !grad_out || !grad_q) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
-  if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
-  hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  if (wu.rc) return wu.rc;
-  const GradPlan gp = grad_plan(ix);
-  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, gp.per_q, false), 4096);
-  int rc;
-  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
-    const int nqc = (int)std::min(cq, nq - q0);
-    const int qtiles = (nqc + kXQ - 1) / kXQ;
-    const size_t nq16 = (size_t)qtiles * kXQ;
-    if ((rc = ix->reserve(nq16 * gp.per_q + 8 * 256))) return rc;
-    Bump b(ix->ws, ix->ws_size);
-    GradCoefArgs ca;
-    float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
-    ca.G = grad_out + q0 * ix->n_sent;
-    HIPCHK(launch_grad_coef(ca, s));
-    if ((rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
-  }
+// The weight gradient of one chunk (cwq_lweight.hip) from the coefficient pass's hL / cI and
+// the raw sums the exact passes left: the chunk's S_int and sraw (EPI_RAW over the leaf rows).
+size_t lw_grad_bytes_per_q(const cwq_index* ix) {   // sraw is counted by the caller (nq_pad lines)
+  return (size_t)lw_parts(ix->NL, ix->NI) * (ix->max_depth + 1) * 8;
+}
+int lw_grad(const cwq_index* ix, const Chunk& c, const GradCoefArgs& ca, const float* sraw, bool is_lp, double* part,
+            int n_w, float* grad_w, hipStream_t s) {
+  LwGradArgs g;
+  memset(&g, 0, sizeof(g));
+  g.nq = ca.nq;
+  g.qtiles = ca.qtiles;
+  g.NL = ix->NL;
+  g.NI = ix->NI;
+  g.nlev = ix->max_depth + 1;
+  g.n_w = n_w;
+  g.hL = ca.hL;
+  g.cI = ca.cI;
+  g.S_row = sraw;
+  g.ldS_row = std::max(ix->NL, 1);
+  g.S_int = c.S_int;
+  g.ldS_int = std::max(ix->NI, 1);
+  g.logdet_row = is_lp ? nullptr : ix->logdet_row;
+  g.logdet_int = ix->logdet_int;
+  g.row_depth = ix->row_depth;
+  g.int_depth = ix->int_depth;
+  g.part = part;
+  g.grad_w = grad_w;
+  HIPCHK(launch_lw_grad(g, s));
   return CWQ_OK;
 }
 
-// Cross-entropy ranking loss over all sentence scores with its gradient, the target's score
-// and rank (cwq_loss.hip, DESIGN.md §4.12): the exact scan's row keys stay in the workspace,
-// the softmax goes straight into the backward's coefficient layout.
-extern "C" int cwq_rank_ce(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
-                           float* loss, float* grad_q, float* target_score, int64_t* rank, void* stream) {
-  if (!ix || !q || !target || !loss) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
-  if (!std::isfinite(temperature) || !(temperature > 0.f))
-    return fail(CWQ_ERR_ARG, "temperature must be finite and > 0");
+// Backward of cwq_rank_scores (cwq_grad.hip): the coefficient pass, the streaming reduction
+// over the three row classes, the slab sum.  Needs q, grad_out and the index only; the weight
+// gradient also needs the forward's raw sums, which it recomputes (internal pass + EPI_RAW).
+int rank_scores_backward_impl(cwq_index* ix, const float* q, int64_t nq, const float* grad_out, const float* level_w,
+                              int n_w, float* grad_q, float* grad_w, void* stream) {
   if (nq == 0) return CWQ_OK;
   std::lock_guard<std::mutex> lk(ix->mu);
   DevGuard dg(ix->device);
@@ -3157,12 +3211,66 @@ extern "C" int cwq_rank_ce(cwq_index* ix, const float* q, int64_t nq, const int6
   WsUse wu(ix, s);
   ScanCfgScope scs(nq);
   if (wu.rc) return wu.rc;
+  if (grad_w && ix->max_depth + 1 > kLwMaxLevels) return fail(CWQ_ERR_ARG, "weight gradient: tree deeper than 64 levels");
+  const GradPlan gp = grad_plan(ix);
+  const int NL = ix->NL;
+  const size_t lw_q = grad_w ? (size_t)std::max(NL, 1) * 4 + lw_grad_bytes_per_q(ix) : 0;
+  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, gp.per_q + lw_q, false), 4096);
+  int rc;
+  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
+    const int nqc = (int)std::min(cq, nq - q0);
+    const int64_t nq_pad = round_up(nqc, kQPad);
+    const int qtiles = (nqc + kXQ - 1) / kXQ;
+    const size_t nq16 = (size_t)qtiles * kXQ;
+    if ((rc = ix->reserve(nq16 * gp.per_q + 8 * 256 + lw_operand_bytes(ix, level_w) +
+                          (grad_w ? chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(NL, 1) * 4 +
+                                        nq16 * lw_grad_bytes_per_q(ix) + 8 * 256
+                                  : 0))))
+      return rc;
+    Bump b(ix->ws, ix->ws_size);
+    GradCoefArgs ca;
+    float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
+    if ((rc = lw_operands(ix, b, level_w, n_w, &ca.meta, &ca.w_int, s))) return rc;
+    ca.G = grad_out + q0 * ix->n_sent;
+    HIPCHK(launch_grad_coef(ca, s));
+    if (grad_q && (rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
+    if (!grad_w) continue;
+    Chunk c;
+    carve_chunk(ix, b, c, nqc, false);
+    float* sraw = b.take<float>((size_t)nq_pad * std::max(NL, 1));
+    double* lwp = b.take<double>(nq16 * lw_grad_bytes_per_q(ix) / 8);
+    HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
+    if ((rc = run_internal(ix, c, s, false))) return rc;
+    if ((rc = run_leaf_scan(ix, c, EPI_RAW, false, 16, 0.f, sraw, NL, nullptr, nullptr, nullptr, 1, nullptr, s)))
+      return rc;
+    if ((rc = lw_grad(ix, c, ca, sraw, false, lwp, n_w, grad_w + q0 * n_w, s))) return rc;
+  }
+  return CWQ_OK;
+}
+
+// Cross-entropy ranking loss over all sentence scores with its gradient, the target's score
+// and rank (cwq_loss.hip, DESIGN.md §4.12): the exact scan's row keys stay in the workspace,
+// the softmax goes straight into the backward's coefficient layout.
+int rank_ce_impl(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
+                 const float* level_w, int n_w, float* loss, float* grad_q, float* grad_w, float* target_score,
+                 int64_t* rank, void* stream) {
+  if (nq == 0) return CWQ_OK;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DevGuard dg(ix->device);
+  hipStream_t s = (hipStream_t)stream;
+  WsUse wu(ix, s);
+  ScanCfgScope scs(nq);
+  if (wu.rc) return wu.rc;
+  if (grad_w && ix->max_depth + 1 > kLwMaxLevels) return fail(CWQ_ERR_ARG, "weight gradient: tree deeper than 64 levels");
   const int NL = ix->NL;
   const int npart = (NL + kCePart - 1) / kCePart;
   const GradPlan gp = grad_plan(ix);
-  // per query: its row keys, the partials and (m, 1/z, row); the backward's arrays when wanted
+  const bool grad = grad_q || grad_w;
+  // per query: its row keys, the partials and (m, 1/z, row); the backward's arrays when wanted;
+  // the rows' raw sums and the fp64 partial lines of the weight gradient
   const size_t ce_q = (size_t)std::max(npart, 1) * 12 + 12;
-  const size_t per_q = (size_t)std::max(NL, 1) * 4 + ce_q + (grad_q ? gp.per_q : 0);
+  const size_t lw_q = grad_w ? (size_t)std::max(NL, 1) * 4 + lw_grad_bytes_per_q(ix) : 0;
+  const size_t per_q = (size_t)std::max(NL, 1) * 4 + ce_q + (grad ? gp.per_q : 0) + lw_q;
   const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, per_q, false), 4096);
   int rc;
   for (int64_t q0 = 0; q0 < nq; q0 += cq) {
@@ -3171,7 +3279,9 @@ extern "C" int cwq_rank_ce(cwq_index* ix, const float* q, int64_t nq, const int6
     const int qtiles = (nqc + kXQ - 1) / kXQ;
     const size_t nq16 = (size_t)qtiles * kXQ;
     if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(NL, 1) * 4 + nq16 * ce_q +
-                          (grad_q ? nq16 * gp.per_q : 0) + 24 * 256)))
+                          (grad ? nq16 * gp.per_q : 0) + 24 * 256 + lw_operand_bytes(ix, level_w) +
+                          (grad_w ? (size_t)nq_pad * std::max(NL, 1) * 4 + nq16 * lw_grad_bytes_per_q(ix) + 4 * 256
+                                  : 0))))
       return rc;
     Bump b(ix->ws, ix->ws_size);
     Chunk c;
@@ -3200,19 +3310,67 @@ extern "C" int cwq_rank_ce(cwq_index* ix, const float* q, int64_t nq, const int6
     a.loss = loss + q0;
     a.tscore = target_score ? target_score + q0 : nullptr;
     a.rank = rank ? rank + q0 : nullptr;
+    if ((rc = lw_operands(ix, b, level_w, n_w, &c.meta, &c.w_int, s))) return rc;
+    // the weight gradient reads every row's lp': the scan writes it beside the key (EPI_KEYLP)
+    float* rowlp = grad_w ? b.take<float>((size_t)nq_pad * std::max(NL, 1)) : nullptr;
     HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
     if ((rc = run_internal(ix, c, s, false))) return rc;
-    if ((rc = run_leaf_scan(ix, c, EPI_KEY, false, 16, 0.f, rowkey, NL, nullptr, nullptr, nullptr, 1, nullptr, s)))
+    if ((rc = run_leaf_scan(ix, c, grad_w ? EPI_KEYLP : EPI_KEY, false, 16, 0.f, rowkey, NL, rowlp, nullptr, nullptr, 1,
+                            nullptr, s)))
       return rc;
     HIPCHK(launch_ce_reduce(a, s));
-    if (!grad_q) continue;
+    if (!grad) continue;
     GradCoefArgs ca;
     float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
-    HIPCHK(launch_ce_coef(a, ix->row_meta, ix->NL_iso, ca.coefL, ca.hL, s));
+    ca.meta = c.meta;
+    ca.w_int = c.w_int;
+    HIPCHK(launch_ce_coef(a, ca.meta, ix->NL_iso, ca.coefL, ca.hL, s));
     HIPCHK(launch_grad_tree(ca, s));
-    if ((rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
+    if (grad_q && (rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
+    if (!grad_w) continue;
+    double* lwp = b.take<double>(nq16 * lw_grad_bytes_per_q(ix) / 8);
+    if ((rc = lw_grad(ix, c, ca, rowlp, true, lwp, n_w, grad_w + q0 * n_w, s))) return rc;
   }
   return CWQ_OK;
+}
+
+}  // namespace
+
+extern "C" int cwq_rank_scores_backward(cwq_index* ix, const float* q, int64_t nq, const float* grad_out,
+                                        float* grad_q, void* stream) {
+  if (!ix || !q || !grad_out || !grad_q) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
+  return rank_scores_backward_impl(ix, q, nq, grad_out, nullptr, 0, grad_q, nullptr, stream);
+}
+
+extern "C" int cwq_rank_scores_backward_w(cwq_index* ix, const float* q, int64_t nq, const float* grad_out,
+                                          const float* level_w, int32_t n_w, float* grad_q, float* grad_w,
+                                          void* stream) {
+  if (!ix || !q || !grad_out || (!grad_q && !grad_w)) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
+  if (int rc = lw_check(level_w, n_w)) return rc;
+  return rank_scores_backward_impl(ix, q, nq, grad_out, level_w, n_w, grad_q, n_w > 0 ? grad_w : nullptr, stream);
+}
+
+extern "C" int cwq_rank_ce(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
+                           float* loss, float* grad_q, float* target_score, int64_t* rank, void* stream) {
+  if (!ix || !q || !target || !loss) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
+  if (!std::isfinite(temperature) || !(temperature > 0.f))
+    return fail(CWQ_ERR_ARG, "temperature must be finite and > 0");
+  return rank_ce_impl(ix, q, nq, target, temperature, nullptr, 0, loss, grad_q, nullptr, target_score, rank, stream);
+}
+
+extern "C" int cwq_rank_ce_w(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
+                             const float* level_w, int32_t n_w, float* loss, float* grad_q, float* grad_w,
+                             float* target_score, int64_t* rank, void* stream) {
+  if (!ix || !q || !target || !loss) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
+  if (int rc = lw_check(level_w, n_w)) return rc;
+  if (!std::isfinite(temperature) || !(temperature > 0.f))
+    return fail(CWQ_ERR_ARG, "temperature must be finite and > 0");
+  return rank_ce_impl(ix, q, nq, target, temperature, level_w, n_w, loss, grad_q, n_w > 0 ? grad_w : nullptr,
+                      target_score, rank, stream);
 }
 
 extern "C" int cwq_node_logprob(cwq_index* ix, const float* q, int64_t nq, int32_t full, float* out, void* stream) {

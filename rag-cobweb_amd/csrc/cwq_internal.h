@@ -19,7 +19,9 @@ struct RowMeta {
   float invL;    // fp32(1 / path_len)
 };
 
-enum Epi { EPI_RAW = 0, EPI_KEY = 1, EPI_TOPK = 2 };
+// EPI_KEYLP: EPI_KEY (Fast keys) that also writes lp' of every row to ScanArgs::pkey, laid out as
+// `out` (the weight gradient of cwq_rank_ce_w reads it: no second pass over the rows)
+enum Epi { EPI_RAW = 0, EPI_KEY = 1, EPI_TOPK = 2, EPI_KEYLP = 3 };
 
 // The exact key of an isotropic row from its raw sum acc = sum_d (x_d - mu_d)^2 (16-dim
 // fma partials summed in slice order): lp = -(logdet + dconst + iv acc)/2, Fast key
@@ -960,6 +962,27 @@ struct CeArgs {
 hipError_t launch_ce_reduce(const CeArgs& a, hipStream_t s);
 // ce_coef_kernel: coefL / hL [qtiles][NL][16] of the loss's gradient (grad_rows_kernel's layout)
 hipError_t launch_ce_coef(const CeArgs& a, const RowMeta* meta, int NL_iso, float* coefL, float* hL, hipStream_t s);
+
+// ---- call-time level weights and their gradient (cwq_lweight.hip) ----
+constexpr int kLwPart = 256;        // rows (nodes) per fp64 partial line: a function of the index alone
+constexpr int kLwMaxLevels = 64;    // level weights a call may pass
+// meta_out[r] = meta[r] with cw = fp32(w[depth_r] / L_r), w_int_out[p] = w[depth_p]; a depth
+// >= n_w weighs 1 (index_create_impl's wdepth): the operands an index built with these weights holds
+hipError_t launch_lw_operands(const float* level_w, int n_w, const RowMeta* meta, const int* row_depth, int NL,
+                              const int* int_depth, int NI, RowMeta* meta_out, float* w_int_out, hipStream_t s);
+int lw_parts(int NL, int NI);       // partial lines per query tile
+struct LwGradArgs {
+  int nq, qtiles, NL, NI, nlev, n_w;   // nlev = max_depth + 1
+  const float* hL; const float* cI;    // [qtiles][NL][16], [qtiles][NI][16] (the backward's coefficient pass)
+  const float* S_row; int64_t ldS_row; // [nq][ldS] the leaf-class rows' raw sums (EPI_RAW), or their lp'
+                                       // (EPI_KEYLP) when logdet_row is null
+  const float* S_int; int64_t ldS_int; // [nq][ldS] raw sums of the internal nodes
+  const float* logdet_row; const float* logdet_int;
+  const int* row_depth; const int* int_depth;
+  double* part;                        // [qtiles][lw_parts][nlev][16]
+  float* grad_w;                       // [nq][n_w]
+};
+hipError_t launch_lw_grad(const LwGradArgs& a, hipStream_t s);
 
 // PCA + ICA whitening (cwq_whiten.hip): C[m][n] = sum_k (A[m][k] - ctr[k]) B[n][k] (/ denom[n])
 hipError_t launch_gemm_nt_f32(const float* A, int64_t M, int K, const float* ctr, const float* B, int N,

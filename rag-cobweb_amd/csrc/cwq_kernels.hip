@@ -266,9 +266,11 @@ __global__ __launch_bounds__(256) void scan_kernel(const float* __restrict__ X, 
             key = fmaf(pp, md.invL, md.cw * lp);
           }
           if (!usable) key = -CWQ_INF;
-          if constexpr (EPI == EPI_KEY) {
-            if (vrow && q < a.nq)
+          if constexpr (EPI == EPI_KEY || EPI == EPI_KEYLP) {
+            if (vrow && q < a.nq) {
               out[(size_t)q * a.ldo + a.out_base + row] = CAT ? (usable ? lp : -CWQ_INF) : key;
+              if constexpr (EPI == EPI_KEYLP) pkey[(size_t)q * a.ldo + a.out_base + row] = lp;
+            }
           } else {
             const int r = qi / QPR;
             const int g = qi % QPR;
@@ -480,6 +482,8 @@ hipError_t launch_scan(bool iso, int epi, bool cat, int kl, const float* X, cons
   CWQ_SCAN(false, EPI_KEY, false)
   CWQ_SCAN(true, EPI_KEY, true)
   CWQ_SCAN(false, EPI_KEY, true)
+  CWQ_SCAN(true, EPI_KEYLP, false)
+  CWQ_SCAN(false, EPI_KEYLP, false)
   CWQ_SCAN(true, EPI_TOPK, false)
   CWQ_SCAN(false, EPI_TOPK, false)
   CWQ_SCAN(true, EPI_TOPK, true)

@@ -324,24 +324,46 @@ class CobwebIndex:
                                           calls.ctypes.data, _stream_raw(self.device.index)))
         return nodes, found, calls
 
-    def rank_scores(self, q):
+    def _level_weights(self, w):
+        """Call-time level weights as a float32 [n_w] tensor on the index device (None: the
+        weights baked into the index).  A device tensor goes through without a host read."""
+        if w is None:
+            return None
+        w = torch.as_tensor(w, dtype=torch.float32).detach()
+        if w.dim() != 1 or w.shape[0] > 64:
+            raise ValueError("level_weights must be a vector of at most 64 values")
+        return w.to(self.device).contiguous()
+
+    def rank_scores(self, q, level_weights=None):
         """All sentence scores (A8), [nq, n_sent].  A tensor that requires grad (with grad
         enabled) gets scores with autograd history (autograd.RankScores: the backward is
-        cwq_rank_scores_backward); the gradient arrives on q's own device and dtype."""
-        if torch.is_tensor(q) and q.requires_grad and torch.is_grad_enabled():
+        cwq_rank_scores_backward); the gradient arrives on q's own device and dtype.
+        level_weights [n_w] (a depth >= n_w weighs 1.0): the scores under these level weights
+        instead of the index's own, bit for bit those of an index built with them; it may
+        require grad too (cwq_rank_scores_w)."""
+        if torch.is_grad_enabled() and ((torch.is_tensor(q) and q.requires_grad) or
+                                        (torch.is_tensor(level_weights) and level_weights.requires_grad)):
             from .autograd import rank_scores_autograd
-            return rank_scores_autograd(self, q)
+            return rank_scores_autograd(self, torch.as_tensor(q), level_weights)
         q = self._queries(q)
+        w = self._level_weights(level_weights)
         out = torch.empty((q.shape[0], self.n_sent), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            check(self._L.cwq_rank_scores(self._h, _ptr(q), q.shape[0], _ptr(out), _stream(self.device)))
+            if w is None:
+                check(self._L.cwq_rank_scores(self._h, _ptr(q), q.shape[0], _ptr(out), _stream(self.device)))
+            elif q.shape[0] > 0:
+                check(self._L.cwq_rank_scores_w(self._h, _ptr(q), q.shape[0], _ptr(w) if w.numel() else None,
+                                                w.numel(), _ptr(out), _stream(self.device)))
         return out
 
-    def rank_scores_backward(self, q, grad_out):
+    def rank_scores_backward(self, q, grad_out, level_weights=None, weight_grad=False, query_grad=True):
         """Gradient of rank_scores with respect to the queries: grad_out [nq, n_sent] (the
         upstream gradient of every score; columns of sentences that are not in the tree are
         never read) -> [nq, dim] float32.  Needs nothing from the forward call; bit-identical
-        from run to run and for a query alone or in a batch."""
+        from run to run and for a query alone or in a batch.
+        level_weights: the gradient under these level weights.  weight_grad=True returns
+        (grad_q, grad_w) with grad_w [nq, n_w] float32, d(sum grad_out * scores[q]) / d w per
+        query (n_w = len(level_weights)); query_grad=False then skips grad_q (None)."""
         q = self._queries(q)
         g = torch.as_tensor(grad_out, dtype=torch.float32)
         if g.dim() == 1:
@@ -349,18 +371,35 @@ class CobwebIndex:
         if g.shape != (q.shape[0], self.n_sent):
             raise ValueError(f"grad_out must be [{q.shape[0]}, {self.n_sent}]")
         g = g.to(self.device).contiguous()
-        out = torch.empty((q.shape[0], self.dim), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._L.cwq_rank_scores_backward(self._h, _ptr(q), q.shape[0], _ptr(g), _ptr(out),
-                                                   _stream(self.device)))
-        return out
+        w = self._level_weights(level_weights)
+        if weight_grad and w is None:
+            raise ValueError("weight_grad needs level_weights (their length sets the gradient's)")
+        if not (weight_grad or query_grad):
+            raise ValueError("nothing to compute")
+        nq = q.shape[0]
+        out = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device) if query_grad or not weight_grad else None
+        if w is None:
+            with torch.cuda.device(self.device):
+                check(self._L.cwq_rank_scores_backward(self._h, _ptr(q), nq, _ptr(g), _ptr(out), _stream(self.device)))
+            return out
+        n_w = w.numel()
+        gw = torch.zeros((nq, n_w), dtype=torch.float32, device=self.device) if weight_grad else None
+        if nq > 0:
+            with torch.cuda.device(self.device):
+                check(self._L.cwq_rank_scores_backward_w(
+                    self._h, _ptr(q), nq, _ptr(g), _ptr(w) if n_w else None, n_w, _ptr(out) if out is not None else None,
+                    _ptr(gw) if weight_grad and n_w else None, _stream(self.device)))
+        return (out, gw) if weight_grad else out
 
-    def rank_ce(self, q, target, temperature=1.0, grad=False):
+    def rank_ce(self, q, target, temperature=1.0, grad=False, level_weights=None, weight_grad=False):
         """Cross-entropy ranking loss over all sentence scores (cwq_rank_ce): q [nq, dim],
         target [nq] sentence ids -> (loss [nq] = logsumexp(scores / T) - scores[target] / T,
         grad_q [nq, dim] = d loss / d q or None when grad is False, target_score [nq], rank [nq]
         int64: the target's 1-based position in score_topk's order).  No [nq, n_sent] tensor is
-        made.  A target outside the tree: loss inf, a zero gradient row, score -inf, rank -1."""
+        made.  A target outside the tree: loss inf, a zero gradient row, score -inf, rank -1.
+        level_weights [n_w]: everything under these level weights instead of the index's own
+        (cwq_rank_ce_w); weight_grad=True appends grad_w [nq, n_w] = d loss / d w per query to
+        the returned tuple."""
         q = self._queries(q)
         nq = q.shape[0]
         t = torch.as_tensor(target)
@@ -372,16 +411,27 @@ class CobwebIndex:
         temperature = float(temperature)
         if not (np.isfinite(temperature) and temperature > 0):
             raise ValueError("temperature must be finite and > 0")
+        w = self._level_weights(level_weights)
+        if weight_grad and w is None:
+            raise ValueError("weight_grad needs level_weights (their length sets the gradient's)")
         loss = torch.empty(nq, dtype=torch.float32, device=self.device)
         tscore = torch.empty(nq, dtype=torch.float32, device=self.device)
         rank = torch.empty(nq, dtype=torch.int64, device=self.device)
         gq = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device) if grad else None
+        gw = torch.zeros((nq, w.numel()), dtype=torch.float32, device=self.device) if weight_grad else None
         if nq == 0:   # empty tensors have no device pointer to pass
-            return loss, gq, tscore, rank
+            return (loss, gq, tscore, rank, gw) if weight_grad else (loss, gq, tscore, rank)
         with torch.cuda.device(self.device):
-            check(self._L.cwq_rank_ce(self._h, _ptr(q), nq, _ptr(t), temperature, _ptr(loss),
-                                      _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank), _stream(self.device)))
-        return loss, gq, tscore, rank
+            if w is None:
+                check(self._L.cwq_rank_ce(self._h, _ptr(q), nq, _ptr(t), temperature, _ptr(loss),
+                                          _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank), _stream(self.device)))
+            else:
+                n_w = w.numel()
+                check(self._L.cwq_rank_ce_w(self._h, _ptr(q), nq, _ptr(t), temperature, _ptr(w) if n_w else None, n_w,
+                                            _ptr(loss), _ptr(gq) if grad else None,
+                                            _ptr(gw) if weight_grad and n_w else None, _ptr(tscore), _ptr(rank),
+                                            _stream(self.device)))
+        return (loss, gq, tscore, rank, gw) if weight_grad else (loss, gq, tscore, rank)
 
     def node_logprob(self, q, full=False):
         """Per-node log-likelihood in BFS order: lp' (full=False) or log_prob (full=True)."""

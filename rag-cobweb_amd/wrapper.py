@@ -306,34 +306,51 @@ class CobwebWrapper:
             return torch.empty(0, device=self.device)
         return self._index.rank_scores(x.reshape(1, -1))[0]
 
-    def cobweb_rank_scores_batch(self, queries):
+    def cobweb_rank_scores_batch(self, queries, level_weights=None):
         """[Q, D] queries -> [Q, n_sentences] scores, differentiable like cobweb_rank_scores:
         one pass over the node means forward and one backward for the whole block (a training
-        step of 16 queries streams them once, not 16 times)."""
+        step of 16 queries streams them once, not 16 times).
+        level_weights (a vector of up to 64 values, depth >= its length weighs 1.0): the scores
+        under these level weights instead of the ones set by set_level_weights, without
+        rebuilding the index, and differentiable in them too (a tensor that requires grad)."""
         self.build_prediction_index()
-        return self._index.rank_scores(queries)
+        if level_weights is None:
+            return self._index.rank_scores(queries)
+        return self._index.rank_scores(queries, level_weights)
 
-    def cobweb_ranking_loss(self, queries, labels, temperature=1.0, reduction="mean"):
+    def cobweb_ranking_loss(self, queries, labels, temperature=1.0, reduction="mean", level_weights=None):
         """FixedDocsRankingLoss.forward (src/training/cobweb_query_train.py:104-126) for a
         block: [Q, D] query embeddings and [Q] labels (sentence ids) -> CrossEntropyLoss(
         cobweb_rank_scores(q) / temperature, label) averaged over the batch ("mean", the
         reference), summed ("sum") or per query ("none").  Differentiable with respect to
         `queries`; the scores are never materialised (cwq_rank_ce: one forward scan, and one
-        backward stream when a gradient is wanted)."""
+        backward stream when a gradient is wanted).
+        level_weights: the loss under these level weights (see cobweb_rank_scores_batch); an
+        nn.Parameter here is learned by any torch optimiser against the fixed index, and
+        written back once with set_level_weights(w.tolist())."""
         if reduction not in ("mean", "sum", "none"):
             raise ValueError('reduction must be "mean", "sum" or "none"')
         self.build_prediction_index()
         from .autograd import rank_ce_autograd
-        loss, _, _ = rank_ce_autograd(self._index, torch.as_tensor(queries), labels, temperature)
+        if level_weights is None:
+            loss, _, _ = rank_ce_autograd(self._index, torch.as_tensor(queries), labels, temperature)
+        else:
+            loss, _, _ = rank_ce_autograd(self._index, torch.as_tensor(queries), labels, temperature, level_weights)
         return loss if reduction == "none" else loss.mean() if reduction == "mean" else loss.sum()
 
-    def cobweb_target_ranks(self, queries, labels):
+    def cobweb_target_ranks(self, queries, labels, level_weights=None):
         """evaluate()'s two per-query numbers (src/training/cobweb_query_train.py:213-304)
         without forming a ranking: (rank [Q] int64, the 1-based position of the label in the
-        Fast ranking -- -1 for a label outside the tree --, true_score [Q])."""
+        Fast ranking -- -1 for a label outside the tree --, true_score [Q]).
+        level_weights: the ranks under these level weights (recall / MRR of a schedule sweep
+        against a fixed index)."""
         self.build_prediction_index()
         with torch.no_grad():
-            _, _, tscore, rank = self._index.rank_ce(torch.as_tensor(queries).detach(), labels)
+            if level_weights is None:
+                _, _, tscore, rank = self._index.rank_ce(torch.as_tensor(queries).detach(), labels)
+            else:
+                _, _, tscore, rank = self._index.rank_ce(torch.as_tensor(queries).detach(), labels,
+                                                         level_weights=level_weights)
         return rank, tscore
 
     def cobweb_predict(self, input, k=5, return_ids=False, is_embedding=False):

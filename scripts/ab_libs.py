@@ -10,6 +10,11 @@ that every arm returns the same ids/scores.  GPU only.
 An arm may carry run-time knobs: `lib.so@CWQ_FG_CUTS=32,128;CWQ_FG_SAMPLE_DIV=128` sets
 those variables while that arm's index is built and while it runs (arms are separated
 by spaces when knobs contain commas: pass --libs once per arm).
+
+    python scripts/ab_libs.py --libs a.so,b.so --rank-ce 1,16,256
+
+--rank-ce times cwq_rank_ce with its gradient instead (HIP events, the arms taking turns inside
+every repetition) and checks that the arms return the same bits.
 """
 import argparse
 import contextlib
@@ -38,6 +43,31 @@ def env(kv):
                 os.environ[k] = v
 
 
+def rank_ce_ab(paths, arms, Q, nqs, reps):
+    gen = torch.Generator(device=Q.device).manual_seed(7)
+    T = float(arms[0].rank_scores(Q[:1]).std())
+    for nq in nqs:
+        q = Q[:nq].contiguous()
+        labels = torch.randint(0, arms[0].n_sent, (nq,), device=Q.device, generator=gen)
+        outs = [ix.rank_ce(q, labels, T, grad=True) for ix in arms]
+        same = all(torch.equal(a, b) for o in outs[1:] for a, b in zip(o, outs[0]))
+        torch.cuda.synchronize()
+        ts = [[] for _ in arms]
+        for _ in range(reps):
+            for i, ix in enumerate(arms):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                ix.rank_ce(q, labels, T, grad=True)
+                b.record()
+                b.synchronize()
+                ts[i].append(a.elapsed_time(b))
+        med = [statistics.median(t) for t in ts]
+        for p, t, m in zip(paths, ts, med):
+            print(f"rank_ce nq={nq} {os.path.basename(p)[:60]}: {m:.3f} ms [{min(t):.3f}, {max(t):.3f}]  "
+                  f"x{m / med[0]:.4f} vs first, own spread {(max(t) - min(t)) / m:.1%}  "
+                  f"{'same bits' if same else 'MISMATCH'}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--libs", required=True, action="append")
@@ -48,6 +78,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--share-index", action="store_true",
                     help="one index for every arm (same library; knobs read per call only)")
+    ap.add_argument("--rank-ce", default="", help="query counts: time rank_ce (loss + grad_q) per arm instead")
+    ap.add_argument("--reps", type=int, default=9, help="--rank-ce: repetitions")
     ap.add_argument("--clusters", type=int, default=0, help="0: flat tree; G: root -> G random clusters -> leaves")
     args = ap.parse_args()
     pkg = cobweb_pkg.load()
@@ -76,11 +108,15 @@ def main():
         with env(knobs[p]):
             L._lib = L.load_library(os.path.abspath(p.split("@")[0]), strict=False)
             ix = pkg.index.CobwebIndex(fs["mean"], fs["var"], fs["parent"], fs["node_of_sentence"], device=dev)
-            ix.set_filter(1)
-            ix.score_topk(Q, args.k)
+            if not args.rank_ce:
+                ix.set_filter(1)
+                ix.score_topk(Q, args.k)
         arms.append(ix)
     del fs
     torch.cuda.empty_cache()
+    if args.rank_ce:
+        rank_ce_ab(paths, arms, Q, [int(v) for v in args.rank_ce.split(",")], args.reps)
+        return
     call = {p: [] for p in paths}
     fg = {p: [] for p in paths}
     ref = None

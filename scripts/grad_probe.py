@@ -16,6 +16,13 @@ would otherwise run) at --torch-n rows on the same GPU.
 process: per nq the median [min, max] of --reps alternating runs of (a) rank_scores with grad ->
 F.cross_entropy(reduction="sum") -> backward, (b) rank_ce with its gradient, (c) the
 forward-only pair, and the peak of torch.cuda.max_memory_allocated() across (a) and across (b).
+
+    python scripts/grad_probe.py --lw --n 1000000 --nq 1,16,256
+
+--lw measures the call-time level weights (cwq_rank_ce_w), paths taking turns
+in this one process: (a) rank_ce with grad_q only (the index's own weights), (b) rank_ce with
+call-time weights and grad_q, (c) the same with grad_q and grad_w, (d) / (e) the forward-only
+calls without and with call-time weights.
 """
 import argparse
 import os
@@ -133,6 +140,32 @@ def ce_probe(ix, Q, nqs, reps, T, tag):
               f"grad (a) vs (b) max rel L2 {rel:.3g}", flush=True)
 
 
+def lw_probe(ix, Q, nqs, reps, T, tag):
+    """--lw: what call-time level weights and their gradient add to a rank_ce training step."""
+    dev = ix.device
+    gen = torch.Generator(device=dev).manual_seed(7)
+    w = torch.ones(ix.info["max_depth"] + 1, device=dev)
+    for nq in nqs:
+        q = Q[:nq].contiguous()
+        labels = torch.randint(0, ix.n_sent, (nq,), device=dev, generator=gen)
+        fns = (lambda: ix.rank_ce(q, labels, T, grad=True),
+               lambda: ix.rank_ce(q, labels, T, grad=True, level_weights=w),
+               lambda: ix.rank_ce(q, labels, T, grad=True, level_weights=w, weight_grad=True),
+               lambda: ix.rank_ce(q, labels, T),
+               lambda: ix.rank_ce(q, labels, T, level_weights=w))
+        a, b, c = fns[0](), fns[1](), fns[2]()
+        assert all(torch.equal(x, y) for x, y in zip(a, b)) and all(torch.equal(x, y) for x, y in zip(a, c[:4]))
+        assert torch.equal(c[4], fns[2]()[4])
+        ta, tb, tc, td, te = event_all(fns, reps)
+        spread = max((t[2] - t[1]) / t[0] for t in (ta, tb, tc))
+        print(f"lweight {tag} nq={nq}: (a) rank_ce grad_q {ta[0]:.3f} ms [{ta[1]:.3f}, {ta[2]:.3f}]  "
+              f"(b) + call-time weights {tb[0]:.3f} ms [{tb[1]:.3f}, {tb[2]:.3f}]  "
+              f"(c) + grad_w {tc[0]:.3f} ms [{tc[1]:.3f}, {tc[2]:.3f}]  b/a {tb[0] / ta[0]:.3f}  c/a {tc[0] / ta[0]:.3f}  "
+              f"spread {spread:.1%}", flush=True)
+        print(f"lweight {tag} nq={nq}: forward only (d) baked weights {td[0]:.3f} ms [{td[1]:.3f}, {td[2]:.3f}]  "
+              f"(e) call-time weights {te[0]:.3f} ms [{te[1]:.3f}, {te[2]:.3f}]  e/d {te[0] / td[0]:.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
@@ -142,7 +175,9 @@ def main():
     ap.add_argument("--torch-n", type=int, default=100_000)
     ap.add_argument("--ce", action="store_true", help="the fused ranking loss (rank_ce) against rank_scores + "
                     "torch cross_entropy, in this one process")
-    ap.add_argument("--temperature", type=float, default=0.0, help="--ce: 0 = the standard deviation of the "
+    ap.add_argument("--lw", action="store_true", help="call-time level weights and their gradient (rank_ce_w) "
+                    "against rank_ce, in this one process")
+    ap.add_argument("--temperature", type=float, default=0.0, help="--ce / --lw: 0 = the standard deviation of the "
                     "first query's scores")
     args = ap.parse_args()
     pkg = cobweb_pkg.load()
@@ -152,12 +187,12 @@ def main():
     nqs = [int(v) for v in args.nq.split(",")]
     Q, _ = pkg.synth.synthetic_queries(X, max(max(nqs), 16), seed=1)
     del X
-    if args.ce:
+    if args.ce or args.lw:
         ix = pkg.index.CobwebIndex(fs["mean"], fs["var"], fs["parent"], fs["node_of_sentence"], device=dev)
         del fs
         torch.cuda.empty_cache()
         T = args.temperature or float(ix.rank_scores(Q[:1]).std())
-        ce_probe(ix, Q, nqs, args.reps, T, f"n={args.n} d={args.dim}")
+        (ce_probe if args.ce else lw_probe)(ix, Q, nqs, args.reps, T, f"n={args.n} d={args.dim}")
         print("done", flush=True)
         return
     tn = min(args.torch_n, args.n)
