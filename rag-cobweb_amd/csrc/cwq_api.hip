@@ -36,6 +36,17 @@ static int fail(int code, const std::string& msg) {
   return code;
 }
 
+// Run-time knobs (environment variables, read where they are used: tests switch them in-process)
+static int env_int(const char* name, int dflt) {   // the value of a non-empty setting, else dflt
+  const char* e = getenv(name);
+  return e && *e ? atoi(e) : dflt;
+}
+static bool env_off(const char* name) {   // a non-empty setting that parses to 0
+  const char* e = getenv(name);
+  return e && *e && atoi(e) == 0;
+}
+static bool env_set(const char* name) { return getenv(name) != nullptr; }
+
 #define HIPCHK(expr)                                                                                \
   do {                                                                                              \
     hipError_t _e = (expr);                                                                         \
@@ -70,6 +81,43 @@ struct Bump {
 };
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+// A grow-on-demand buffer of the handle: kept between calls, freed and allocated anew (rounded up
+// to `round` bytes) when a call needs more than it holds.  busy: an event to wait for before the
+// free -- earlier calls' kernels may still read a device buffer (cwq_index::busy).
+struct GrowBuf {
+  enum Kind { kDevice, kPinned, kMapped };   // hipMalloc / pinned host / mapped coherent host memory
+  Kind kind;
+  size_t round;
+  const char* what;   // the error message; one that ends in '(' gets the size appended
+  void* p = nullptr;
+  size_t size = 0;
+  template <class T>
+  T* as() const {
+    return (T*)p;
+  }
+  void release() {
+    if (p) (void)(kind == kDevice ? hipFree(p) : hipHostFree(p));
+    p = nullptr;
+    size = 0;
+  }
+  int reserve(size_t b, hipEvent_t busy = nullptr) {
+    if (b <= size) return CWQ_OK;
+    if (busy) (void)hipEventSynchronize(busy);
+    release();
+    b = (size_t)round_up((int64_t)b, (int64_t)round);
+    const hipError_t e = kind == kDevice   ? hipMalloc(&p, b)
+                         : kind == kPinned ? hipHostMalloc(&p, b, hipHostMallocDefault)
+                                           : hipHostMalloc(&p, b, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) {
+      std::string msg = what;
+      if (msg.back() == '(') msg += std::to_string(b) + " B)";
+      return fail(CWQ_ERR_OOM, msg);
+    }
+    size = b;
+    return CWQ_OK;
+  }
+};
 
 }  // namespace
 
@@ -227,27 +275,24 @@ struct cwq_index {
   // stream and the next call makes its own stream wait for it (ws_begin / ws_end):
   // calls on different streams reuse the workspace in order.
   std::mutex mu;
-  void* ws = nullptr;
-  size_t ws_size = 0;
+  GrowBuf ws{GrowBuf::kDevice, 1 << 20, "workspace hipMalloc failed ("};
   size_t ws_budget = 0;   // query-chunk workspace budget, from the free memory at the first call
   hipEvent_t ws_ev = nullptr;
   bool ws_ev_live = false;
   bool ws_idle = false;   // set by a call that ends with its stream synchronized: no event needed
-  int* hflags = nullptr;   // pinned host copy of the per-query filter flags (one D2H per chunk)
-  size_t hflags_n = 0;
+  // the per-query filter flags on the host (int): coherent (fine-grained) memory --
+  // final_wide_kernel writes the flags of the per-call path straight into it; the batch paths
+  // copy into it (one D2H per chunk)
+  GrowBuf hflags{GrowBuf::kMapped, 1, "hipHostMalloc failed"};
   // cwq_score_topk_host: pinned staging of the host queries, their device copy, and mapped
   // (coherent) host memory the kernels write the results into
-  void* hq = nullptr;
-  void* dq = nullptr;
-  size_t hq_n = 0;
-  void* hout = nullptr;
-  size_t hout_n = 0;
+  GrowBuf hq{GrowBuf::kPinned, 1 << 16, "host query staging allocation failed"};
+  GrowBuf dq{GrowBuf::kDevice, 1 << 16, "host query staging allocation failed"};
+  GrowBuf hout{GrowBuf::kMapped, 1 << 16, "host result buffer allocation failed"};
   // fallback re-runs (cwq_score_topk / cwq_categorize): gathered queries, their results
-  // and the device index lists, kept between calls (grown on demand)
-  void* fb = nullptr;
-  size_t fb_size = 0;
-  void* fb2 = nullptr;    // categorize's filter fallback (its exact re-run uses fb itself)
-  size_t fb2_size = 0;
+  // and the device index lists, kept between calls
+  GrowBuf fb{GrowBuf::kDevice, 1 << 20, "fallback hipMalloc failed ("};
+  GrowBuf fb2{GrowBuf::kDevice, 1, "categorize fallback buffers"};   // categorize's filter fallback (its exact re-run uses fb itself)
 
   template <class T>
   int alloc(T** p, size_t n) {
@@ -266,28 +311,9 @@ struct cwq_index {
     if (!v.empty()) HIPCHK(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
     return CWQ_OK;
   }
-  int reserve(size_t b) {
-    if (b <= ws_size) return CWQ_OK;
-    if (ws_ev_live) (void)hipEventSynchronize(ws_ev);   // earlier calls' kernels may still read it
-    if (ws) (void)hipFree(ws);
-    ws = nullptr;
-    ws_size = 0;
-    b = round_up((int64_t)b, 1 << 20);
-    if (hipMalloc(&ws, b) != hipSuccess) return fail(CWQ_ERR_OOM, "workspace hipMalloc failed (" + std::to_string(b) + " B)");
-    ws_size = b;
-    return CWQ_OK;
-  }
-  int reserve_fb(size_t b) {
-    if (b <= fb_size) return CWQ_OK;
-    if (ws_ev_live) (void)hipEventSynchronize(ws_ev);
-    if (fb) (void)hipFree(fb);
-    fb = nullptr;
-    fb_size = 0;
-    b = round_up((int64_t)b, 1 << 20);
-    if (hipMalloc(&fb, b) != hipSuccess) return fail(CWQ_ERR_OOM, "fallback hipMalloc failed (" + std::to_string(b) + " B)");
-    fb_size = b;
-    return CWQ_OK;
-  }
+  // earlier calls' kernels may still read the device buffers: the event to wait for before a free
+  hipEvent_t busy() const { return ws_ev_live ? ws_ev : nullptr; }
+  int reserve(size_t b) { return ws.reserve(b, busy()); }
   // start of a query call on stream s: wait for the previous call's use of the workspace
   int ws_begin(hipStream_t s) {
     if (!ws_ev && hipEventCreateWithFlags(&ws_ev, hipEventDisableTiming) != hipSuccess)
@@ -322,47 +348,7 @@ struct cwq_index {
     if (ws_ev_live) (void)hipEventSynchronize(ws_ev);
     if (ws_ev) (void)hipEventDestroy(ws_ev);
     for (void* p : allocs) (void)hipFree(p);
-    if (ws) (void)hipFree(ws);
-    if (fb) (void)hipFree(fb);
-    if (fb2) (void)hipFree(fb2);
-    if (hflags) (void)hipHostFree(hflags);
-    if (hq) (void)hipHostFree(hq);
-    if (dq) (void)hipFree(dq);
-    if (hout) (void)hipHostFree(hout);
-  }
-  int host_io(size_t qbytes, size_t obytes) {
-    if (qbytes > hq_n) {
-      if (hq) (void)hipHostFree(hq);
-      if (dq) (void)hipFree(dq);
-      hq = dq = nullptr;
-      hq_n = 0;
-      const size_t b = (size_t)round_up((int64_t)qbytes, 1 << 16);
-      if (hipHostMalloc(&hq, b, hipHostMallocDefault) != hipSuccess || hipMalloc(&dq, b) != hipSuccess)
-        return fail(CWQ_ERR_OOM, "host query staging allocation failed");
-      hq_n = b;
-    }
-    if (obytes > hout_n) {
-      if (hout) (void)hipHostFree(hout);
-      hout = nullptr;
-      hout_n = 0;
-      const size_t b = (size_t)round_up((int64_t)obytes, 1 << 16);
-      if (hipHostMalloc(&hout, b, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-        return fail(CWQ_ERR_OOM, "host result buffer allocation failed");
-      hout_n = b;
-    }
-    return CWQ_OK;
-  }
-  int host_flags(size_t n) {
-    if (n <= hflags_n) return CWQ_OK;
-    if (hflags) (void)hipHostFree(hflags);
-    hflags = nullptr;
-    hflags_n = 0;
-    // coherent (fine-grained) host memory: final_wide_kernel writes the flags of the
-    // per-call path straight into it; the batch paths copy into it
-    if (hipHostMalloc((void**)&hflags, n * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-      return fail(CWQ_ERR_OOM, "hipHostMalloc failed");
-    hflags_n = n;
-    return CWQ_OK;
+    for (GrowBuf* b : {&ws, &fb, &fb2, &hflags, &hq, &dq, &hout}) b->release();
   }
 };
 
@@ -439,8 +425,7 @@ int plan_groups(cwq_index* ix, const float* mean, const int64_t* d_rows, const s
   int rc;
   const int NLi = ix->NL_iso, NI = ix->NI, D = ix->D;
   rgrp.assign(NLi, -1);
-  const char* ge = getenv("CWQ_GROUP_CENTRE");
-  const int force = ge && *ge ? atoi(ge) : -1;
+  const int force = env_int("CWQ_GROUP_CENTRE", -1);
   if (force == 0 || NI < 2 || NLi == 0) return CWQ_OK;
   std::vector<int> idep(NI, 0);
   int maxdep_all = 0;
@@ -448,8 +433,7 @@ int plan_groups(cwq_index* ix, const float* mean, const int64_t* d_rows, const s
     idep[i] = idep[par_int[i]] + 1;   // BFS internal ids: the parent first
     maxdep_all = std::max(maxdep_all, idep[i]);
   }
-  const char* ec = getenv("CWQ_GROUP_CUT");
-  const bool depth1 = ec && *ec && atoi(ec) == 1;
+  const bool depth1 = env_int("CWQ_GROUP_CUT", 0) == 1;
   const char* em = getenv("CWQ_GROUP_MAXDEP");
   const int maxd = depth1 ? 1 : std::max(1, std::min(maxdep_all, em && *em && atoi(em) > 0 ? atoi(em) : 8));
   const int W = maxd + 1;
@@ -708,7 +692,7 @@ int build_filter(cwq_index* ix, const float* mean, const int64_t* d_rows, const 
       }
       T.par_hi = T.par;
       if (T.uniform && !same_par) {
-        if (plo >= 0 && phi - plo < max_parents && !getenv("CWQ_FG_NO_MULTI")) {
+        if (plo >= 0 && phi - plo < max_parents && !env_set("CWQ_FG_NO_MULTI")) {
           T.uniform = 2;
           T.par = plo;
           T.par_hi = phi;
@@ -832,8 +816,7 @@ int build_prune(cwq_index* ix, const float* mean, const VarSrc& var, const std::
                 const std::vector<int>& par_int, const std::vector<float>& w_int, const std::vector<int64_t>& rows,
                 const std::vector<int>& int_id, const std::vector<RowMeta>& meta, const std::vector<int>& row_par,
                 const std::vector<int>& row_flags, hipStream_t s) {
-  const char* e = getenv("CWQ_GROUP_PRUNE");
-  if ((e && *e && atoi(e) == 0) || !ix->grp_mode || ix->G <= 0 || !ix->int_Ar || ix->NI < 2 || ix->DP > 2048)
+  if (env_off("CWQ_GROUP_PRUNE") || !ix->grp_mode || ix->G <= 0 || !ix->int_Ar || ix->NI < 2 || ix->DP > 2048)
     return CWQ_OK;
   const int NI = ix->NI, NL = ix->NL, G = ix->G;
   for (float w : w_int)
@@ -1234,8 +1217,7 @@ int index_create_impl(int device, int64_t n_nodes, int32_t dim, const float* mea
   if (ix->NL_iso > 0 && ix->NI >= 2 && ix->max_depth <= kMaxChain) {
     // internal-node bound operands: K = [x'^2, x'] -> DPB2 = fgemm width of 2*DP
     ix->DPB2 = fgemm_dpb(2 * ix->DP);
-    const char* ep = getenv("CWQ_INT_PATH");
-    ix->int_path = !(ep && *ep && atoi(ep) == 0);
+    ix->int_path = !env_off("CWQ_INT_PATH");
     const float gamma2 = (float)((ix->DPB2 + 64) * std::ldexp(1.0, -23));
     ix->root_w = w_int[0];
     HIPCHK(hipMemcpyAsync(&ix->root_ld, ix->logdet_int, 4, hipMemcpyDeviceToHost, s));
@@ -1435,6 +1417,49 @@ struct ScanCfgScope {
   ~ScanCfgScope() { scan_cfg_end(); }
 };
 
+namespace {
+
+// A query entry point's hold on the handle, in this order: its lock, its device, its use of the
+// workspace on stream s (rc: ws_begin's result) and the call's scan configuration.
+struct QueryCall {
+  std::lock_guard<std::mutex> lk;
+  DevGuard dg;
+  WsUse wu;
+  ScanCfgScope scs;
+  int rc;
+  QueryCall(cwq_index* ix, int64_t nq, hipStream_t s) : lk(ix->mu), dg(ix->device), wu(ix, s), scs(nq), rc(wu.rc) {}
+};
+
+// Gather some queries of a call, run a sub-call on them, scatter its results back: idx holds the
+// queries' indices in the call (pageable host memory, so close() synchronises the stream: idx
+// must outlive its upload to d_idx).
+struct SubCall {
+  hipStream_t s;
+  int64_t n;
+  int64_t* d_idx;
+  int open(const std::vector<int64_t>& idx, int64_t* d, hipStream_t st) {
+    s = st;
+    n = (int64_t)idx.size();
+    d_idx = d;
+    HIPCHK(hipMemcpyAsync(d_idx, idx.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+    return CWQ_OK;
+  }
+  int gather(const float* q, int64_t D, float* qsub) {   // qsub[i] = q[idx[i]]
+    HIPCHK(launch_copy_rows(q, D, d_idx, qsub, D, nullptr, n, D, s));
+    return CWQ_OK;
+  }
+  int scatter(const void* src, int64_t words, void* dst) {   // dst[idx[i]] = src[i], rows of 4-byte words
+    HIPCHK(launch_copy_rows(src, words, nullptr, dst, words, d_idx, n, words, s));
+    return CWQ_OK;
+  }
+  int close() {
+    HIPCHK(hipStreamSynchronize(s));
+    return CWQ_OK;
+  }
+};
+
+}  // namespace
+
 // ---------------------------------------------------------------------------
 // Query orchestration
 // ---------------------------------------------------------------------------
@@ -1477,9 +1502,7 @@ int group_tables(cwq_index* ix, Chunk& c, const float* q, bool cat, hipStream_t 
 // Group pruning (cwq_prune.hip) of a Fast chunk: on by default where the index built its
 // constants (build_prune); CWQ_GROUP_PRUNE=0 turns it off per call (in-process A/Bs).
 bool use_prune(const cwq_index* ix) {
-  if (!ix->prune_ok) return false;
-  const char* e = getenv("CWQ_GROUP_PRUNE");
-  return !(e && *e && atoi(e) == 0);
+  return ix->prune_ok && !env_off("CWQ_GROUP_PRUNE");
 }
 size_t prune_bytes_per_query(const cwq_index* ix) { return ix->prune_ok ? (size_t)ix->G * 36 + 16 : 0; }
 
@@ -1552,7 +1575,7 @@ int prune_internal(cwq_index* ix, Chunk& c, const float* q, int K, Bump& b, hipS
     pa.live = live;
   }
   HIPCHK(launch_prune(pa, ix->cus, ix->prune_nq == 0, s));   // the call's first pruned chunk resets the total
-  if (getenv("CWQ_PRUNE_DEBUG")) {   // diagnostics: the first queries' bounds and thresholds
+  if (env_set("CWQ_PRUNE_DEBUG")) {   // diagnostics: the first queries' bounds and thresholds
     const int n = std::min(nq, 3);
     std::vector<float> kub((size_t)n * G), th(n);
     std::vector<int> gs(n), ctr(8);
@@ -1637,9 +1660,8 @@ constexpr int kChainMaxQ = 64, kChainMaxDepth = 16;
 int internal_prefixes(cwq_index* ix, Chunk& c, hipStream_t s, float* BF, float* LPF, float dfull, const float* q,
                       int grp_cat) {
   const float* w_int = c.w_int ? c.w_int : ix->w_int;
-  const char* fe = getenv("CWQ_INT_FINISH");
   const bool fin = ix->levels.size() > 1 && c.nq <= kChainMaxQ && ix->max_depth <= kChainMaxDepth &&
-                   !(fe && *fe && atoi(fe) == 0);
+                   !env_off("CWQ_INT_FINISH");
   if (!fin) {
     for (auto& lv : ix->levels)
       HIPCHK(launch_prefix_level(c.S_int, ix->NI, c.nq, lv.first, lv.second, ix->par_int, w_int, ix->logdet_int,
@@ -1704,8 +1726,8 @@ int run_internal(cwq_index* ix, Chunk& c, hipStream_t s, bool bf_lpf = true, con
   const int nslab2 = (a.nrows_pad + a.rows_per_slab - 1) / a.rows_per_slab;
   a.out = c.S_int;
   a.ldo = ix->NI;
-  const char* rse = getenv("CWQ_RAW_SPLIT");   // 0: the scan kernel for one query too (A/B)
-  if (c.nq == 1 && (size_t)(ix->DP / 16) * kWave * 4 <= 65536 && !(rse && *rse && atoi(rse) == 0))
+  // CWQ_RAW_SPLIT=0: the scan kernel for one query too (A/B)
+  if (c.nq == 1 && (size_t)(ix->DP / 16) * kWave * 4 <= 65536 && !env_off("CWQ_RAW_SPLIT"))
     HIPCHK(launch_raw_split(c.X, ix->int_A, ix->int_B, a, s));
   else
     HIPCHK(launch_scan(false, EPI_RAW, false, kl, c.X, ix->int_A, ix->int_B, a, nslab2, s));
@@ -1721,8 +1743,7 @@ void fg_groups(int n_qt, int& qg, int& rg);
 bool use_int_bounds(const cwq_index* ix) {
   // group-centred rows need the exact prefixes (their group terms are folded into them)
   if (!ix->int_bounds || ix->NL_an > 0 || ix->grp_mode) return false;
-  const char* e = getenv("CWQ_INT_BOUND");
-  return !(e && *e && atoi(e) == 0);
+  return !env_off("CWQ_INT_BOUND");
 }
 
 size_t int_bounds_bytes(const cwq_index* ix, int64_t nqf) {
@@ -1774,7 +1795,7 @@ int run_internal_bounds(cwq_index* ix, Chunk& c, const float* q, int64_t nqf, Bu
   g.nrows = (int)ix->ld_i2;
   const int nqb = (c.nq + 15) / 16;
   if (ix->int_path && c.nq <= kStreamMaxQ && stream_lds_bytes(nqb, ix->DPB2) <= (size_t)kStreamMaxLds &&
-      !getenv("CWQ_INT_STREAM_OFF")) {
+      !env_set("CWQ_INT_STREAM_OFF")) {
     // a few queries (the per-call path): the path-sum rows streamed once against <= 64
     // queries (stream_kernel<2>) instead of 256-query MFMA tiles that are mostly padding;
     // the same dots and root lines
@@ -1965,7 +1986,7 @@ int64_t chunk_queries(const cwq_index* ix, int64_t nq, size_t per_query_extra, b
   } else {
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) == hipSuccess)
-      budget = std::min<size_t>((size_t)48 << 30, std::max<size_t>((size_t)2 << 30, (fr + ix->ws_size) / 5 * 2));
+      budget = std::min<size_t>((size_t)48 << 30, std::max<size_t>((size_t)2 << 30, (fr + ix->ws.size) / 5 * 2));
     const_cast<cwq_index*>(ix)->ws_budget = budget;
   }
   int64_t c = (int64_t)std::max<size_t>(kQPad, budget / std::max<size_t>(per_q, 1));
@@ -2031,10 +2052,7 @@ void note_filter(cwq_index* ix) {
 
 // fgemm launch geometry: query groups over the 8 XCDs (each keeps its query panel in
 // L2), row groups for the remaining factor.
-int fg_phases() {
-  const char* e = getenv("CWQ_FG_PHASES");
-  return e && *e ? atoi(e) : 1;
-}
+int fg_phases() { return env_int("CWQ_FG_PHASES", 1); }
 
 // filter phases over the row tiles: cut points at n_rt * f / 1024 for the fractions f in
 // CWQ_FG_CUTS (comma separated, increasing, at most 4; default 32,96,256,512: five
@@ -2061,10 +2079,7 @@ int fg_phase_cuts(int n_rt, int* cuts) {
   return n;
 }
 
-int fg_order() {   // default: dynamic per-XCD tile claims (measured fastest)
-  const char* e = getenv("CWQ_FG_ORDER");
-  return e && *e ? atoi(e) : 2;
-}
+int fg_order() { return env_int("CWQ_FG_ORDER", 2); }   // default: dynamic per-XCD tile claims (measured fastest)
 
 // XCD split of the tiles: qg query groups x rg row groups (qg * rg = 8).  Default: all 8
 // XCDs split the queries (each keeps its query panels in its L2 and streams every row
@@ -2103,20 +2118,17 @@ int rerun_exact(cwq_index* ix, const float* q, const std::vector<int64_t>& qi, i
   const size_t D = (size_t)ix->D;
   const size_t o_tq = round_up(n * 8, 256), o_tid = o_tq + round_up(n * D * 4, 256),
                o_ts = o_tid + round_up((int64_t)n * k * 8, 256), tot = o_ts + round_up((int64_t)n * k * 4, 256);
-  int rc = ix->reserve_fb(tot);
+  int rc = ix->fb.reserve(tot, ix->busy());
   if (rc) return rc;
-  char* fb = (char*)ix->fb;
-  int64_t* d_idx = (int64_t*)fb;
+  char* fb = ix->fb.as<char>();
   float* tq = (float*)(fb + o_tq);
   int64_t* tid = (int64_t*)(fb + o_tid);
   float* ts = scores ? (float*)(fb + o_ts) : nullptr;
-  HIPCHK(hipMemcpyAsync(d_idx, qi.data(), n * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(launch_copy_rows(q, (int64_t)D, d_idx, tq, (int64_t)D, nullptr, n, (int64_t)D, s));
+  SubCall g;
+  if ((rc = g.open(qi, (int64_t*)fb, s)) || (rc = g.gather(q, (int64_t)D, tq))) return rc;
   if ((rc = score_topk_impl(ix, tq, n, k, tid, ts, s, false))) return rc;
-  HIPCHK(launch_copy_rows(tid, 2 * (int64_t)k, nullptr, ids, 2 * (int64_t)k, d_idx, n, 2 * (int64_t)k, s));
-  if (scores) HIPCHK(launch_copy_rows(ts, k, nullptr, scores, k, d_idx, n, k, s));
-  HIPCHK(hipStreamSynchronize(s));   // qi (pageable host memory) must outlive the upload
-  return CWQ_OK;
+  if ((rc = g.scatter(tid, 2 * (int64_t)k, ids)) || (scores && (rc = g.scatter(ts, k, scores)))) return rc;
+  return g.close();
 }
 
 // Small-batch path (cwq_stream.hip): nq <= kStreamMaxQ queries, isotropic rows through
@@ -2125,8 +2137,7 @@ int rerun_exact(cwq_index* ix, const float* q, const std::vector<int64_t>& qi, i
 bool use_stream(const cwq_index* ix, int64_t nq, int k) {
   if (nq > kStreamMaxQ || k > kFiltMaxK || !ix->iso_Mb) return false;
   if (stream_lds_bytes((int)((nq + 15) / 16), ix->DPB) > (size_t)kStreamMaxLds) return false;
-  const char* e = getenv("CWQ_STREAM");
-  return !(e && *e && atoi(e) == 0);
+  return !env_off("CWQ_STREAM");
 }
 
 // The stream filter's int8 row panel (half the bf16 panel's bytes per row; the per-call pass
@@ -2162,9 +2173,9 @@ bool build_i8(cwq_index* ix, hipStream_t s) {
 }
 bool i8_size_rule(const cwq_index* ix) { return (int64_t)ix->NL_iso * ix->DPB >= kI8MinBytes; }
 bool ensure_i8(cwq_index* ix, hipStream_t s) {
-  const char* e = getenv("CWQ_STREAM_I8");
-  if ((e && *e && atoi(e) == 0) || ix->grp_mode) return false;
-  if (!(e && *e && atoi(e) == 1) && !i8_size_rule(ix)) return false;
+  const int e = env_int("CWQ_STREAM_I8", -1);
+  if (e == 0 || ix->grp_mode) return false;
+  if (e != 1 && !i8_size_rule(ix)) return false;
   return build_i8(ix, s);
 }
 
@@ -2191,8 +2202,7 @@ int fg_i8_from(cwq_index* ix, const int* cuts, int nph, bool cat, bool ib, hipSt
     const int v = atoi(e);
     return v >= 0 && build_i8(ix, s) ? std::min(v, nph) : nph;
   }
-  const char* ee = getenv("CWQ_FG_I8_EARLY");
-  const int ev = ee && *ee ? atoi(ee) : -1;
+  const int ev = env_int("CWQ_FG_I8_EARLY", -1);
   if ((ev < 0 ? ix->i8_by_size : ev > 0) && ix->n_hub > 0 && !ix->i8_early_off && build_i8(ix, s)) {
     ix->i8_early_ran = true;
     return 0;
@@ -2209,10 +2219,7 @@ void note_i8_early(cwq_index* ix, int64_t nq, int64_t cand_sum, int64_t n_fallba
 }
 
 // CWQ_SELECT_UNFUSED=1: the per-call path keeps select_kernel (and sb_prep) -- A/B only
-bool sel_unfused() {
-  const char* e = getenv("CWQ_SELECT_UNFUSED");
-  return e && *e && atoi(e) != 0;
-}
+bool sel_unfused() { return env_int("CWQ_SELECT_UNFUSED", 0) != 0; }
 
 // Workgroups of the per-call filter pass: one per CU (8 waves); CWQ_STREAM_WGS = m runs m
 // per CU (more loads in flight on short passes -- an A/B knob).
@@ -2257,12 +2264,11 @@ int stream_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64
   // tail and its radix T2 it pays at a few queries (nq 1 / 8: 670 -> 601 / 722 -> 664 us) and
   // not at 64 (1373 -> 3161 us), profiles/r05_percall_b4d9_i8_ab.log.  CWQ_STREAM_I8=1 / 0
   // forces it on / off.
-  const char* e8 = getenv("CWQ_STREAM_I8");
-  const int e8v = e8 && *e8 ? atoi(e8) : -1;
+  const int e8v = env_int("CWQ_STREAM_I8", -1);
   const bool i8 = e8v != 0 && (!ib || nqc <= 8 || e8v == 1) && ensure_i8(ix, s);
   int rc;
   if ((rc = ix->reserve(need))) return rc;
-  Bump b(ix->ws, ix->ws_size);
+  Bump b(ix->ws.p, ix->ws.size);
   Chunk c;
   carve_chunk(ix, b, c, nqc, false);
   float* pkey = b.take<float>((size_t)nq_pad * slabs * K);
@@ -2297,7 +2303,7 @@ int stream_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64
   // one fused prep launch when the exact internal pass is small (flat trees: the root)
   bool fused = !ib && ix->NI <= kSbMaxNI && (int)ix->levels.size() <= kSbMaxNI &&
                ((size_t)2 * std::max(ix->DP, ix->DPB) + (size_t)ix->NI * (ix->DP / 16) + ix->NI) * 4 <= 65536 &&
-               !getenv("CWQ_SB_UNFUSED");
+               !env_set("CWQ_SB_UNFUSED");
   SbPrepArgs sp;
   const bool prn = !ib && use_prune(ix);
   int* live = nullptr;   // group pruning: the filter's 16-row blocks
@@ -2339,9 +2345,8 @@ int stream_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64
   // with fprep) -- one launch less, but measured slower (C2 one query per call 101.5 ->
   // 104.9 us: the probe's workgroups all wait for the prep, profiles/r04_percall_ab_c2_v1.log),
   // so opt-in: CWQ_PROBE_PREP=1
-  const char* fpe = getenv("CWQ_PROBE_PREP");
   const bool fprep = fused && ix->NI == 1 && nqb == 1 && !i8 && ix->DP <= 1024 && !sel_unfused() &&
-                     (fpe && *fpe && atoi(fpe) == 1);
+                     env_int("CWQ_PROBE_PREP", 0) == 1;
   if (fprep && !ix->sel_ctr)   // the fused select's counter (lives across calls)
     if ((rc = ix->alloc(&ix->sel_ctr, 1))) return rc;
   if (fprep) {
@@ -2423,8 +2428,7 @@ int stream_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64
   a.T0 = tl;
   a.ldT0 = 64;
   if (ix->timing) HIPCHK(hipEventRecord(ix->ev[4], s));
-  const char* lve = getenv("CWQ_PRUNE_LIVE");   // 0: the pass over every block (A/B)
-  const bool use_live = live && !(lve && *lve && atoi(lve) == 0);
+  const bool use_live = live && !env_off("CWQ_PRUNE_LIVE");   // 0: the pass over every block (A/B)
   // the select runs in the probe launch's last workgroup (one launch less per call);
   // CWQ_SELECT_UNFUSED=1 keeps select_kernel (same thresholds: both run select_wave)
   const bool fsel = !sel_unfused();
@@ -2483,13 +2487,14 @@ int stream_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64
   if ((rc = run_leaf_scan(ix, c, EPI_TOPK, false, kl, 0.f, nullptr, 0, pkey, paux, prow, K, &nst, s, 2, 1, slabs)))
     return rc;
   const IntChain chain = int_chain(ix);
-  if ((rc = ix->host_flags((size_t)3 * nqc))) return rc;
+  if ((rc = ix->hflags.reserve((size_t)3 * nqc * sizeof(int)))) return rc;
+  int* hflags = ix->hflags.as<int>();
   // one candidate list per query (no anisotropic rows): final_wide expands the top-K to
   // sentence ids and writes the host flags itself (no merge launch, no flag copy)
-  const bool ftail = nst == 1 && final_wide_rows(ix->DP, capq) > 0 && !getenv("CWQ_FW_UNFUSED");
+  const bool ftail = nst == 1 && final_wide_rows(ix->DP, capq) > 0 && !env_set("CWQ_FW_UNFUSED");
   // okf / nex: the split tail's arrival count and exact-rerank sum (zeroed with the counters;
   // the fused tail reports through hflags, not these)
-  const FwExpand fx{ix->sent_ptr, ix->sent_ids, ids, scores, k, ix->hflags, fws, fsk, fsa, fsr};
+  const FwExpand fx{ix->sent_ptr, ix->sent_ids, ids, scores, k, hflags, fws, fsk, fsa, fsr};
   HIPCHK(launch_final(c.X, ix->iso_Mf, ix->DP, nqc, K, capq, qcnt, qover, crow, cu, cl, T, 1, ix->row_meta,
                       ix->row_par, c.P ? c.P : ix->dummy, c.pT ? 1 : c.ldP, 0, pkey, paux, prow, (int64_t)nst * K, okf,
                       nex, lkb, lrb, done, ib ? &chain : nullptr, 0, 0.f, s, ftail ? &fx : nullptr));
@@ -2497,16 +2502,16 @@ int stream_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64
   if (ix->timing) HIPCHK(hipEventRecord(ix->ev[2], s));
   if (!ftail) {
     HIPCHK(launch_merge_expand(pkey, paux, prow, nqc, nst * K, K, k, ix->sent_ptr, ix->sent_ids, ids, scores, s));
-    HIPCHK(hipMemcpyAsync(ix->hflags, qcnt, (size_t)3 * nqc * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hflags, qcnt, (size_t)3 * nqc * 4, hipMemcpyDeviceToHost, s));
   }
   if (ix->timing) HIPCHK(hipEventRecord(ix->ev[3], s));
   HIPCHK(sync_spin(s));
   std::vector<int64_t> redo;
   int64_t cand_sum = 0, exact_sum = 0;
   for (int i = 0; i < nqc; ++i) {
-    if (!ix->hflags[nqc + i]) redo.push_back(i);
-    cand_sum += ix->hflags[i];
-    exact_sum += ix->hflags[2 * nqc + i];
+    if (!hflags[nqc + i]) redo.push_back(i);
+    cand_sum += hflags[i];
+    exact_sum += hflags[2 * nqc + i];
   }
   if (ix->timing) {
     float e[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2597,7 +2602,7 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
   fg_groups(n_qt, g.qgroups, g.rgroups);
   g.qinfo = qinfo;
   g.order = fg_order();
-  g.dbg = getenv("CWQ_FG_DBG") ? atoi(getenv("CWQ_FG_DBG")) : 0;
+  g.dbg = env_int("CWQ_FG_DBG", 0);
   g.tctr = gctr + 8;
   g.rf = cat ? ix->cat_rf : ix->iso_rf;
   g.tf = cat ? ix->cat_tf : ix->iso_tf;
@@ -2662,7 +2667,7 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
     g.rt_off = cuts[ph];
     g.n_rt = cuts[ph + 1] - cuts[ph];
     const std::vector<int>& up = cat ? ix->cat_uni_prefix : ix->tile_uni_prefix;
-    g.all_uniform = up[cuts[ph + 1]] - up[cuts[ph]] == g.n_rt && !getenv("CWQ_FG_NO_ALLUNI");
+    g.all_uniform = up[cuts[ph + 1]] - up[cuts[ph]] == g.n_rt && !env_set("CWQ_FG_NO_ALLUNI");
     // all-uniform Fast-key launches append raw records; the bucket pass evaluates their
     // bounds (the categorize tables keep the in-kernel bounds: their key is min'ed with
     // the bottleneck table per survivor)
@@ -2763,7 +2768,7 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
     if (ib) need += int_bounds_bytes(ix, nqf);
     const bool prn = filt && !ib && !general && use_prune(ix);
     if ((rc = ix->reserve(need))) return rc;
-    Bump b(ix->ws, ix->ws_size);
+    Bump b(ix->ws.p, ix->ws.size);
     Chunk c;
     carve_chunk(ix, b, c, nqc, false);
     if (ix->timing) HIPCHK(hipEventRecord(ix->ev[0], s));
@@ -2817,10 +2822,10 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
       HIPCHK(launch_merge_expand(pkey, paux, prow, nqc, nst * K, K, k, ix->sent_ptr, ix->sent_ids, ids + q0 * k,
                                  scores ? scores + q0 * k : nullptr, s));
       if (filt) {
-        if ((rc = ix->host_flags((size_t)3 * nqf))) return rc;
-        HIPCHK(hipMemcpyAsync(ix->hflags, qcnt_d, (size_t)3 * nqf * 4, hipMemcpyDeviceToHost, s));
+        if ((rc = ix->hflags.reserve((size_t)3 * nqf * sizeof(int)))) return rc;
+        HIPCHK(hipMemcpyAsync(ix->hflags.p, qcnt_d, (size_t)3 * nqf * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        const int* cnth = ix->hflags;
+        const int* cnth = ix->hflags.as<int>();
         const int* okh = cnth + nqf;
         const int* nexh = cnth + 2 * nqf;
         for (int i = 0; i < nqc; ++i) {
@@ -2879,20 +2884,36 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
 
 }  // namespace
 
-extern "C" int cwq_score_topk(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,
-                              void* stream) {
+// The paired entry points (device / host memory) open alike: the argument checks; then, under the
+// call's hold on the handle (QueryCall), the last call's record cleared.
+static int topk_args(const cwq_index* ix, const float* q, int64_t nq, int32_t k, const int64_t* ids) {
   if (!ix || (!q && nq > 0) || (!ids && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
   if (k <= 0) return fail(CWQ_ERR_ARG, "k must be >= 1");
-  if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
+  return CWQ_OK;
+}
+static void topk_reset(cwq_index* ix) {
   for (float& t : ix->t_ms) t = 0.f;
   for (int64_t& t : ix->stats) t = 0;
   ix->prune_nq = 0;
+}
+// The host entry points' staging: the queries through pinned memory into ix->dq, room for
+// obytes of results in the mapped host memory ix->hout
+static int stage_host(cwq_index* ix, const float* q, size_t qbytes, size_t obytes, hipStream_t s) {
+  int rc;
+  if ((rc = ix->hq.reserve(qbytes)) || (rc = ix->dq.reserve(qbytes)) || (rc = ix->hout.reserve(obytes))) return rc;
+  memcpy(ix->hq.p, q, qbytes);
+  HIPCHK(hipMemcpyAsync(ix->dq.p, ix->hq.p, qbytes, hipMemcpyHostToDevice, s));
+  return CWQ_OK;
+}
+
+extern "C" int cwq_score_topk(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,
+                              void* stream) {
+  if (int rc = topk_args(ix, q, nq, k, ids)) return rc;
+  if (nq == 0) return CWQ_OK;
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  topk_reset(ix);
+  if (call.rc) return call.rc;
   const int rc = score_topk_impl(ix, q, nq, k, ids, scores, s, true);
   if (!rc) note_filter(ix);
   return rc;
@@ -2905,26 +2926,18 @@ extern "C" int cwq_score_topk(cwq_index* ix, const float* q, int64_t nq, int32_t
 // device-to-host copy per call.
 extern "C" int cwq_score_topk_host(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,
                                    void* stream) {
-  if (!ix || (!q && nq > 0) || (!ids && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (k <= 0) return fail(CWQ_ERR_ARG, "k must be >= 1");
+  if (int rc = topk_args(ix, q, nq, k, ids)) return rc;
   if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
-  for (float& t : ix->t_ms) t = 0.f;
-  for (int64_t& t : ix->stats) t = 0;
-  ix->prune_nq = 0;
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  topk_reset(ix);
+  if (call.rc) return call.rc;
   const size_t qb = (size_t)nq * ix->D * 4, ib = (size_t)round_up(nq * k * 8, 256), sb = (size_t)nq * k * 4;
   int rc;
-  if ((rc = ix->host_io(qb, ib + sb))) return rc;
-  memcpy(ix->hq, q, qb);
-  HIPCHK(hipMemcpyAsync(ix->dq, ix->hq, qb, hipMemcpyHostToDevice, s));
-  int64_t* hid = (int64_t*)ix->hout;
-  float* hsc = (float*)((char*)ix->hout + ib);
-  if ((rc = score_topk_impl(ix, (const float*)ix->dq, nq, k, hid, hsc, s, true))) return rc;
+  if ((rc = stage_host(ix, q, qb, ib + sb, s))) return rc;
+  int64_t* hid = ix->hout.as<int64_t>();
+  float* hsc = (float*)(ix->hout.as<char>() + ib);
+  if ((rc = score_topk_impl(ix, ix->dq.as<float>(), nq, k, hid, hsc, s, true))) return rc;
   note_filter(ix);
   HIPCHK(sync_spin(s));
   ix->ws_idle = true;   // synchronized
@@ -3030,12 +3043,9 @@ namespace {
 int rank_scores_impl(cwq_index* ix, const float* q, int64_t nq, const float* level_w, int n_w, float* out,
                      void* stream) {
   if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  if (call.rc) return call.rc;
   const int64_t cq = chunk_queries(ix, nq, (size_t)ix->NL * 4, false);
   int rc;
   for (int64_t q0 = 0; q0 < nq; q0 += cq) {
@@ -3044,7 +3054,7 @@ int rank_scores_impl(cwq_index* ix, const float* q, int64_t nq, const float* lev
     if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(ix->NL, 1) * 4 + 8 * 256 +
                           lw_operand_bytes(ix, level_w))))
       return rc;
-    Bump b(ix->ws, ix->ws_size);
+    Bump b(ix->ws.p, ix->ws.size);
     Chunk c;
     carve_chunk(ix, b, c, nqc, false);
     float* rowkey = b.take<float>((size_t)nq_pad * std::max(ix->NL, 1));
@@ -3205,12 +3215,9 @@ int lw_grad(const cwq_index* ix, const Chunk& c, const GradCoefArgs& ca, const f
 int rank_scores_backward_impl(cwq_index* ix, const float* q, int64_t nq, const float* grad_out, const float* level_w,
                               int n_w, float* grad_q, float* grad_w, void* stream) {
   if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  if (call.rc) return call.rc;
   if (grad_w && ix->max_depth + 1 > kLwMaxLevels) return fail(CWQ_ERR_ARG, "weight gradient: tree deeper than 64 levels");
   const GradPlan gp = grad_plan(ix);
   const int NL = ix->NL;
@@ -3227,7 +3234,7 @@ int rank_scores_backward_impl(cwq_index* ix, const float* q, int64_t nq, const f
                                         nq16 * lw_grad_bytes_per_q(ix) + 8 * 256
                                   : 0))))
       return rc;
-    Bump b(ix->ws, ix->ws_size);
+    Bump b(ix->ws.p, ix->ws.size);
     GradCoefArgs ca;
     float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
     if ((rc = lw_operands(ix, b, level_w, n_w, &ca.meta, &ca.w_int, s))) return rc;
@@ -3255,12 +3262,9 @@ int rank_ce_impl(cwq_index* ix, const float* q, int64_t nq, const int64_t* targe
                  const float* level_w, int n_w, float* loss, float* grad_q, float* grad_w, float* target_score,
                  int64_t* rank, void* stream) {
   if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  if (call.rc) return call.rc;
   if (grad_w && ix->max_depth + 1 > kLwMaxLevels) return fail(CWQ_ERR_ARG, "weight gradient: tree deeper than 64 levels");
   const int NL = ix->NL;
   const int npart = (NL + kCePart - 1) / kCePart;
@@ -3283,7 +3287,7 @@ int rank_ce_impl(cwq_index* ix, const float* q, int64_t nq, const int64_t* targe
                           (grad_w ? (size_t)nq_pad * std::max(NL, 1) * 4 + nq16 * lw_grad_bytes_per_q(ix) + 4 * 256
                                   : 0))))
       return rc;
-    Bump b(ix->ws, ix->ws_size);
+    Bump b(ix->ws.p, ix->ws.size);
     Chunk c;
     carve_chunk(ix, b, c, nqc, false);
     float* rowkey = b.take<float>((size_t)nq_pad * std::max(NL, 1));
@@ -3376,12 +3380,9 @@ extern "C" int cwq_rank_ce_w(cwq_index* ix, const float* q, int64_t nq, const in
 extern "C" int cwq_node_logprob(cwq_index* ix, const float* q, int64_t nq, int32_t full, float* out, void* stream) {
   if (!ix || (!q && nq > 0) || (!out && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
   if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  if (call.rc) return call.rc;
   const float dconst = full ? (float)((double)ix->D * (double)logf(2.0f * (float)M_PI)) : 0.f;
   const int64_t cq = chunk_queries(ix, nq, (size_t)ix->NL * 4);
   int rc;
@@ -3389,7 +3390,7 @@ extern "C" int cwq_node_logprob(cwq_index* ix, const float* q, int64_t nq, int32
     const int nqc = (int)std::min(cq, nq - q0);
     const int64_t nq_pad = round_up(nqc, kQPad);
     if ((rc = ix->reserve(chunk_bytes(ix, nq_pad) + (size_t)nq_pad * std::max(ix->NL, 1) * 4 + 8 * 256))) return rc;
-    Bump b(ix->ws, ix->ws_size);
+    Bump b(ix->ws.p, ix->ws.size);
     Chunk c;
     carve_chunk(ix, b, c, nqc);
     float* sleaf = b.take<float>((size_t)nq_pad * std::max(ix->NL, 1));
@@ -3409,16 +3410,13 @@ extern "C" int cwq_prefix_bounds(cwq_index* ix, const float* q, int64_t nq, floa
   if (nq <= 0 || nq > 4096) return fail(CWQ_ERR_ARG, "nq must be in [1, 4096]");
   if (!ix->int_bounds)
     return fail(CWQ_ERR_ARG, "no internal-node bounds on this index (flat tree, no isotropic leaf rows or too deep)");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  if (call.rc) return call.rc;
   const int64_t nq_pad = round_up(nq, kQPad), nqf = round_up(nq, kFgTile);
   int rc;
   if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + int_bounds_bytes(ix, nqf) + 64 * 256))) return rc;
-  Bump b(ix->ws, ix->ws_size);
+  Bump b(ix->ws.p, ix->ws.size);
   Chunk c;
   carve_chunk(ix, b, c, (int)nq, false);
   const size_t n = (size_t)nq * ix->NI * 4;
@@ -3443,9 +3441,6 @@ extern "C" int cwq_prefix_bounds(cwq_index* ix, const float* q, int64_t nq, floa
 }
 
 namespace {
-// cwq_categorize body.  allow_filter: the isotropic leaf rows go through the bf16-MFMA
-// filter with the categorize key (run_iso_filter, cat); queries whose candidate lists
-// overflow are re-run with allow_filter = false (the exact scan of every leaf row).
 // Categorize's top-R row list for a few queries (nq <= kStreamMaxQ) through the per-call
 // stream filter instead of the batch pipeline (sample pass, select, five fgemm launches with
 // bucket / tighten): query prep, probe + fused select, one pass, final_wide_kernel with the
@@ -3470,7 +3465,7 @@ size_t stream_cat_bytes(const cwq_index* ix, int nqc) {
 bool stream_cat_ok(const cwq_index* ix, int nqc, int R) {
   return ix->iso_Mb && ix->NL_iso >= kStreamMinRows && nqc <= kStreamMaxQ && R <= kFiltMaxK &&
          stream_lds_bytes((nqc + 15) / 16, ix->DPB) <= (size_t)kStreamMaxLds && final_wide_rows(ix->DP, kFgCapQ) > 0 &&
-         !getenv("CWQ_CAT_STREAM_OFF");
+         !env_set("CWQ_CAT_STREAM_OFF");
 }
 int stream_cat_list(cwq_index* ix, Chunk& c, const float* q, int nqc, int R, const float* BFk, float dfull, float* pkey,
                     float* paux, int* prow, int64_t lstride, int* okf, Bump& b, hipStream_t s) {
@@ -3534,7 +3529,7 @@ int stream_cat_list(cwq_index* ix, Chunk& c, const float* q, int nqc, int R, con
   const int64_t n_probe = cat_n_probe(ix, R);
   a.probe_stride = std::max<int64_t>(1, ngroups / std::max<int64_t>(n_probe, 1));
   a.n_probe = std::min<int64_t>(n_probe, (ngroups + a.probe_stride - 1) / a.probe_stride);
-  a.probe_rows = getenv("CWQ_CAT_PROBE_MAX") ? 0 : 1;   // 1: group maxima (A/B)
+  a.probe_rows = env_set("CWQ_CAT_PROBE_MAX") ? 0 : 1;   // 1: group maxima (A/B)
   a.lb = lb;
   a.ldlb = ldlb;
   a.T0 = tl;
@@ -3549,7 +3544,7 @@ int stream_cat_list(cwq_index* ix, Chunk& c, const float* q, int nqc, int R, con
   HIPCHK(launch_final(c.X, ix->iso_Mf, ix->DP, nqc, R, capq, qcnt, qover, crow, cu, cl, T, 1, ix->row_meta, ix->row_par,
                       BFk ? BFk : ix->dummy, std::max(ix->NI, 1), 0, pkey, paux, prow, lstride, okf, nex, lkb, lrb,
                       done, nullptr, 1, dfull, s, fws > 1 ? &fx : nullptr));
-  if (getenv("CWQ_CAT_DEBUG")) {   // diagnostics: per query candidates, overflow, threshold, certified
+  if (env_set("CWQ_CAT_DEBUG")) {   // diagnostics: per query candidates, overflow, threshold, certified
     std::vector<int> hc(nqc), ho(nqc), hk(nqc), hx(nqc);
     std::vector<float> ht(nqc), hl(64);
     HIPCHK(hipMemcpyAsync(hc.data(), qcnt, nqc * 4, hipMemcpyDeviceToHost, s));
@@ -3570,614 +3565,668 @@ int stream_cat_list(cwq_index* ix, Chunk& c, const float* q, int nqc, int R, con
 constexpr int kCatCountRetry = 16;   // (cwq_index::cat_count_idle)
 constexpr int kCatExplore = 32, kCatDenseMemory = 64;   // (cwq_index::cat_ema_*)
 constexpr int kLzFanout = 1024;   // batches try the lazy path when no node has more children
-int categorize_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t max_nodes, int64_t* nodes,
-                    int32_t* n_found, int64_t* n_calls, hipStream_t s, bool allow_filter) {
-  const float dfull = (float)((double)ix->D * (double)logf(2.0f * (float)M_PI));
-  const int R = std::max(1, std::min(64, ix->NL));
-  const bool complete = ix->NL <= R;
-  const int64_t cap_list = 1 + (int64_t)ix->NI + R;
-  const int kl = 64;
-  int rc;
-  const char* ce = getenv("CWQ_CAT_FILTER");
-  // a call of a few queries takes the per-call stream lists from kStreamMinRows rows on (as
-  // Fast does): the exact 64-wide list scan of a small tree is its latency chain -- qqp1k
-  // (1,000 rows x 1,024): 285 us a list, profiles/r05_published_shapes_v4.log
-  const bool filt = allow_filter && use_filter(ix, R, nq <= 64 ? kStreamMinRows : kFiltMinRows, false) &&
-                    !(ce && *ce && atoi(ce) == 0);
-  const int n_rt = filt ? (int)(ix->ld_f / kFgTile) : 0;
-  const size_t filt_q = filt ? iso_filter_bytes_per_query(ix, n_rt) : 0;
-  const int nqb_est = n_qblocks_for(nq, kl);
-  auto n_slabs = [&](int nqb) {
+constexpr int kl = 64;            // the scan's list width
+
+// What a categorize_impl call fixes before its chunk loop, and what its chunks add up.
+struct CatCall {
+  cwq_index* ix;
+  const float* q;
+  int64_t nq;
+  int k;
+  int64_t max_nodes;
+  int64_t* nodes;
+  int32_t* n_found;
+  int64_t* n_calls;
+  hipStream_t s;
+  float dfull;
+  int R;           // list length
+  bool complete;   // the list holds every leaf row
+  int64_t cap_list, cap2, cap_dense;   // heap entries per query: list replay, two-level replay, DENSE
+  bool filt;       // list 1 through the filter
+  size_t filt_q;   // (its workspace bytes per query)
+  int64_t cq;      // queries per chunk
+  bool scat, small2;   // the two-level replay in place on the chunk: stream lists / exact-scan lists
+  int pk;          // the policy slot: small call / batch
+  bool measure, direct;
+  std::vector<int64_t> fredo;   // queries the filter could not certify
+  int64_t n_dense = 0;          // queries the list paths left to the DENSE re-run
+
+  int n_slabs(int nqb) const {
     return filt ? 1 + (pick_nslab(ix, ix->NL_an, nqb) + 1) * scan_lists_per_slab(kl)
                 : (pick_nslab(ix, ix->NL_iso, nqb) + pick_nslab(ix, ix->NL_an, nqb) + 2) * scan_lists_per_slab(kl);
-  };
-  const int max_slabs = n_slabs(nqb_est);
-  int64_t cq = chunk_queries(ix, nq, (size_t)cap_list * 16 + (size_t)max_slabs * R * 12 + R * 12 + filt_q);
-  if (filt && cq < nq) cq = std::max<int64_t>(kFgTile, cq / kFgTile * kFgTile);   // whole query tiles
-  std::vector<int64_t> fredo;   // queries the filter could not certify
-  // a few queries (the reference's one cobweb_predict per query): the lists through the
-  // per-call stream filter (stream_cat_list), and a two-level replay of every query of the
-  // call reuses the chunk's internal pass instead of gathering and recomputing it
-  const bool scat = filt && nq <= cq && stream_cat_ok(ix, (int)nq, R);
-  // a few queries without the filter (small trees): the two-level replay on the chunk too,
-  // list 2 by the exact scan (instead of gathering the queries and re-running the internal
-  // pass: qqp1k's Basic call 1.02 ms, profiles/r05_published_shapes_v3.log)
-  const bool small2 = !filt && nq <= std::min<int64_t>(cq, 64);
-  // every query resolved in the first chunk by the list paths: the flag gathers cleared the
-  // node tails after the last results, so the caller needs no clear_tail launch / sync
-  ix->cat_tail_done = nq <= cq;
-  const int64_t cap2 = 1 + (int64_t)ix->NI + 2 * R;
-  // straight to the exact lazy replay (a call of <= 64 queries; CWQ_CAT_DIRECT=0 / 1: never /
-  // always where it applies)
-  const char* cde = getenv("CWQ_CAT_DIRECT");
-  const int cdv = cde && *cde ? atoi(cde) : -1;
-  const int64_t cap_dense = 1 + (int64_t)ix->NI + ix->NL;
-  const int pk = nq <= 64 ? 0 : 1;   // the policy slot: small call / batch
-  const bool direct_ok = (pk == 1 || nq <= cq) && ix->NI > 0 && ix->DP <= 2048;
-  const bool top = allow_filter;   // (not the filter-overflow re-run of a call)
-  const bool measure = direct_ok && cdv < 0 && top;
-  bool direct = false;
-  if (direct_ok) {
-    if (cdv >= 0) {
-      direct = cdv == 1;
-    } else if (!top) {
-      direct = ix->cat_pref_direct[pk];
-    } else {
-      ++ix->cat_pol_calls[pk];
-      const bool may = ix->cat_dense_seen > 0 || (pk == 1 && ix->max_fanout <= kLzFanout);
-      if (!may) direct = false;                                     // the lists resolve this tree
-      else if (ix->cat_ema_list[pk] < 0.0) direct = false;          // the lists first
-      else if (ix->cat_ema_direct[pk] < 0.0) direct = true;         // then one trial
-      else direct = (ix->cat_ema_direct[pk] < ix->cat_ema_list[pk]) != (ix->cat_pol_calls[pk] % kCatExplore == 0);
-    }
   }
-  const auto t_call = std::chrono::steady_clock::now();
-  int64_t n_dense_call = 0;
-  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
-    const int nqc = (int)std::min(cq, nq - q0);
-    const int64_t nq_pad = round_up(nqc, kQPad);
-    const int nqb = n_qblocks_for(nqc, kl);
-    const int slabs = n_slabs(nqb);
-    const int64_t nqf = round_up(nqc, kFgTile);
-    size_t need = chunk_bytes(ix, nq_pad) + (size_t)nq_pad * ((size_t)slabs * R * 12 + (size_t)R * 12 +
-                                                              (size_t)cap_list * 16 + 12) + 17 * 256 +
-                  (filt ? (size_t)nqf * filt_q + 4096 * 8 : 0);
-    if (direct && pk == 0) need += (size_t)nq_pad * ((size_t)cap_dense * 16 + 16) + 2 * 256;
-    if (scat || small2)   // + the second list's stream pass, T2, lists and heap (the two-level replay in place)
-      need += (scat ? 2 * stream_cat_bytes(ix, nqc) : 0) + (size_t)nq_pad * ((size_t)std::max(ix->NI, 1) * 4 + (size_t)slabs * R * 12 +
-                                                                 (size_t)R * 12 + (size_t)cap2 * 16 + 16) + 32 * 256;
-    if ((rc = ix->reserve(need))) return rc;
-    Bump b(ix->ws, ix->ws_size);
-    Chunk c;
-    carve_chunk(ix, b, c, nqc);
-    float* pkey = b.take<float>((size_t)nq_pad * slabs * R);
-    float* paux = b.take<float>((size_t)nq_pad * slabs * R);
-    int* prow = b.take<int>((size_t)nq_pad * slabs * R);
-    float* okey = b.take<float>((size_t)nq_pad * R);
-    float* oaux = b.take<float>((size_t)nq_pad * R);
-    int* orow = b.take<int>((size_t)nq_pad * R);
-    HeapEnt* heap = b.take<HeapEnt>((size_t)nq_pad * cap_list);
-    int* status = b.take<int>((size_t)nq_pad);
-    // the replay arguments every path shares (the tree; the per-chunk fields set by the caller)
-    auto base_args = [&]() {
-      SimArgs sd;
-      memset(&sd, 0, sizeof(sd));
-      sd.k = k;
-      sd.max_nodes = max_nodes;
-      sd.NI = ix->NI;
-      sd.NL = ix->NL;
-      sd.ldI = std::max(ix->NI, 1);
-      sd.complete = complete ? 1 : 0;
-      sd.int_child_begin = ix->int_child_begin;
-      sd.int_child_end = ix->int_child_end;
-      sd.int_nchild = ix->int_nchild;
-      sd.int_bfs = ix->int_bfs;
-      sd.int_has_sent = ix->int_has_sent;
-      sd.int_leaf_a0 = ix->int_leaf_a0;
-      sd.int_leaf_a1 = ix->int_leaf_a1;
-      sd.int_leaf_b0 = ix->int_leaf_b0;
-      sd.int_leaf_b1 = ix->int_leaf_b1;
-      sd.row_par = ix->row_par;
-      sd.row_bfs = ix->row_bfs;
-      sd.row_flags = ix->row_flags;
-      sd.par_int = ix->par_int;
-      sd.X = nullptr;
-      sd.DP = ix->DP;
-      sd.Mf = ix->iso_Mf;
-      sd.NL_iso = ix->NL_iso;
-      sd.anA = ix->an_A;
-      sd.anB = ix->an_B;
-      sd.ld_an = ix->ld_an;
-      sd.meta = ix->row_meta;
-      sd.dconst = dfull;
-      return sd;
-    };
-    // the DENSE re-run of the chunk's queries `redo` (chunk-local indices): the exact heap replay
-    // (exact by construction), results scattered into the outputs
-    auto dense_rerun = [&](const std::vector<int>& redo) -> int {
-      ix->cat_tail_done = false;   // the DENSE re-run below writes after the last flag gather
+};
 
-      // DENSE re-run: the exact heap replay of the hard queries (exact by construction).  By
-      // default lazily (simulate_lazy_kernel: a popped node's leaf rows scored when their
-      // parent is popped); CWQ_CAT_LAZY=0: every leaf row materialised first by the exact scan.
-      const char* lze = getenv("CWQ_CAT_LAZY");
-      const bool lazy = !(lze && *lze && atoi(lze) == 0) && ix->DP <= 2048;
-      const int64_t ldL = lazy ? 1 : std::max(ix->NL, 1);
-      const int64_t cap_dense = 1 + (int64_t)ix->NI + ix->NL;
-      const size_t per_q = (size_t)ix->DP * 4 + 4 * (size_t)std::max(ix->NI, 1) * 4 + (size_t)ldL * 4 +
-                           (size_t)cap_dense * 16 + 64 + (size_t)k * 8 + (size_t)ix->D * 4;
-      const int64_t sub = std::max<int64_t>(1, std::min<int64_t>((int64_t)redo.size(), ((size_t)2 << 30) / per_q));
-      std::vector<float> hx;
-      for (size_t r0 = 0; r0 < redo.size(); r0 += sub) {
-        const int ns = (int)std::min<int64_t>(sub, (int64_t)redo.size() - (int64_t)r0);
-        const int64_t ns_pad = round_up(ns, kQPad);
-        // per hard query: dense keys, heap, then status / nodes[k] / found / calls
-        if ((rc = ix->reserve(chunk_bytes(ix, ns_pad) +
-                              (size_t)ns_pad * ((size_t)ldL * 4 + cap_dense * 16 + 64 + (size_t)k * 8) + 16 * 256 +
-                              (size_t)ns_pad * ix->D * 4)))
-          return rc;
-        Bump b2(ix->ws, ix->ws_size);
-        Chunk c2;
-        carve_chunk(ix, b2, c2, ns);
-        float* qsub = b2.take<float>((size_t)ns * ix->D);
-        float* dense = b2.take<float>((size_t)ns_pad * ldL);
-        HeapEnt* heap2 = b2.take<HeapEnt>((size_t)ns_pad * cap_dense);
-        int* status2 = b2.take<int>(ns_pad);
-        int64_t* nodes2 = b2.take<int64_t>((size_t)ns_pad * k);
-        int* found2 = b2.take<int>(ns_pad);
-        int64_t* calls2 = b2.take<int64_t>(ns_pad);
-        std::vector<int64_t> gq(ns);   // global query index of each hard query
-        for (int i = 0; i < ns; ++i) gq[i] = q0 + redo[r0 + i];
-        if ((rc = ix->reserve_fb((size_t)ns * 8))) return rc;
-        int64_t* d_gq = (int64_t*)ix->fb;
-        HIPCHK(hipMemcpyAsync(d_gq, gq.data(), (size_t)ns * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_copy_rows(q, ix->D, d_gq, qsub, ix->D, nullptr, ns, ix->D, s));
-        HIPCHK(launch_pad_queries(qsub, ns, ix->D, c2.X, c2.nq_pad, ix->DP, s));
-        if ((rc = run_internal(ix, c2, s))) return rc;
-        if (!lazy && (rc = run_leaf_scan(ix, c2, EPI_KEY, true, 16, dfull, dense, ix->NL, nullptr, nullptr, nullptr, 1,
-                                         nullptr, s)))
-          return rc;
-        SimArgs sd = base_args();
-        sd.pre_status = 0;   // every hard query replays (status2 is fresh scratch)
-        sd.nq = ns;
-        sd.R = 0;
-        sd.LPF = c2.LPF ? c2.LPF : ix->dummy;
-        sd.BF = c2.BF ? c2.BF : ix->dummy;
-        sd.dense_lpf = dense;
-        sd.ldL = ldL;
-        sd.heap = heap2;
-        sd.heap_cap = cap_dense;
-        sd.out_nodes = nodes2;
-        sd.n_found = found2;
-        sd.n_calls = calls2;
-        sd.status = status2;
-        if (lazy) {
-          sd.X = c2.X;
-          sd.DP = ix->DP;
-          sd.Mf = ix->iso_Mf;
-          sd.NL_iso = ix->NL_iso;
-          sd.anA = ix->an_A;
-          sd.anB = ix->an_B;
-          sd.ld_an = ix->ld_an;
-          sd.meta = ix->row_meta;
-          sd.dconst = dfull;
-          // the run-merge replay in LDS; a query that overflows its arena is re-run on the
-          // global heap (status 1 gates it; the second kernel writes status 0)
-          const char* lre = getenv("CWQ_CAT_LAZY_RUNS");
-          if (!(lre && *lre && atoi(lre) == 0)) {
-            HIPCHK(launch_simulate_lazy_runs(sd, s));
-            sd.pre_status = 1;
-          }
-          HIPCHK(launch_simulate_lazy(sd, s));
-          ix->lazy_stats[1] += ns;
-        } else {
-          HIPCHK(launch_simulate(sd, s));
-        }
-        HIPCHK(launch_copy_rows(nodes2, 2 * (int64_t)k, nullptr, nodes, 2 * (int64_t)k, d_gq, ns, 2 * (int64_t)k, s));
-        HIPCHK(launch_copy_rows(found2, 1, nullptr, n_found, 1, d_gq, ns, 1, s));
-        if (n_calls) HIPCHK(launch_copy_rows(calls2, 2, nullptr, n_calls, 2, d_gq, ns, 2, s));
-        HIPCHK(hipStreamSynchronize(s));   // gq (pageable host memory) must outlive the upload
-      }
-      return CWQ_OK;
-    };
-    HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
-    if ((rc = run_internal(ix, c, s, true, q + q0 * ix->D, direct ? -1 : (filt ? 1 : -1)))) return rc;
-    if (direct) {
-      // the exact replay straight away: every pushed entry scored when its parent is popped
-      SimArgs sd = base_args();
-      sd.nq = nqc;
-      sd.R = 0;
-      sd.LPF = c.LPF ? c.LPF : ix->dummy;
-      sd.BF = c.BF ? c.BF : ix->dummy;
-      sd.out_nodes = nodes + q0 * k;
-      sd.n_found = n_found + q0;
-      sd.n_calls = n_calls ? n_calls + q0 : nullptr;
-      sd.status = status;
-      sd.X = c.X;
-      ix->cat_tail_done = false;
-      if (pk == 0) {   // a few queries: the global-heap form queued behind for arena overflows
-        sd.heap = b.take<HeapEnt>((size_t)nq_pad * cap_dense);
-        sd.heap_cap = cap_dense;
+// The path of a call: the list paths, or straight to the exact lazy replay (a call of <= 64
+// queries, or a batch; CWQ_CAT_DIRECT=0 / 1: never / always where it applies); the choice is
+// measured (cwq_index::cat_ema_*).  top: not the filter-overflow re-run of a call.
+void cat_policy_begin(CatCall& cc, bool top) {
+  cwq_index* ix = cc.ix;
+  const int cdv = env_int("CWQ_CAT_DIRECT", -1);
+  const int pk = cc.pk = cc.nq <= 64 ? 0 : 1;
+  const bool direct_ok = (pk == 1 || cc.nq <= cc.cq) && ix->NI > 0 && ix->DP <= 2048;
+  cc.measure = direct_ok && cdv < 0 && top;
+  cc.direct = false;
+  if (!direct_ok) return;
+  if (cdv >= 0) {
+    cc.direct = cdv == 1;
+  } else if (!top) {
+    cc.direct = ix->cat_pref_direct[pk];
+  } else {
+    ++ix->cat_pol_calls[pk];
+    const bool may = ix->cat_dense_seen > 0 || (pk == 1 && ix->max_fanout <= kLzFanout);
+    if (!may) cc.direct = false;                                     // the lists resolve this tree
+    else if (ix->cat_ema_list[pk] < 0.0) cc.direct = false;          // the lists first
+    else if (ix->cat_ema_direct[pk] < 0.0) cc.direct = true;         // then one trial
+    else cc.direct = (ix->cat_ema_direct[pk] < ix->cat_ema_list[pk]) != (ix->cat_pol_calls[pk] % kCatExplore == 0);
+  }
+}
+
+// After the chunks (and the filter-overflow re-run): the path's per-query wall time, completed
+// (the caller syncs after a small call anyway).  (cat_dense_seen is noted before that re-run;
+// cat_count_idle and cat_two_spec chunk by chunk, where the next chunk reads them.)
+int cat_policy_end(CatCall& cc, std::chrono::steady_clock::time_point t_call) {
+  cwq_index* ix = cc.ix;
+  if (!cc.measure) return CWQ_OK;
+  HIPCHK(hipStreamSynchronize(cc.s));
+  const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count() /
+                    (double)cc.nq;
+  const int pk = cc.pk;
+  double& ema = cc.direct ? ix->cat_ema_direct[pk] : ix->cat_ema_list[pk];
+  ema = ema < 0.0 ? us : 0.75 * ema + 0.25 * us;
+  ix->cat_pref_direct[pk] = ix->cat_ema_direct[pk] >= 0.0 && ix->cat_ema_list[pk] >= 0.0 &&
+                            ix->cat_ema_direct[pk] < ix->cat_ema_list[pk];
+  return CWQ_OK;
+}
+
+// The replay arguments every path starts from: the call, the tree, the internal-node tables of
+// the chunk c and the outputs of its nq queries.  The caller sets what differs: the lists (R),
+// the heap, the status and its gates, the queries X (lazy replay) or the dense keys.
+// DP, Mf, NL_iso, anA, anB, ld_an, meta and dconst are the lazy replay's operands: only
+// launch_simulate_lazy / launch_simulate_lazy_runs and their kernels read or check them.
+// launch_simulate, launch_cat_count and launch_simulate_two (whose sites left them zero before
+// this builder) ignore them; a check on one of them added to those launchers would change that.
+SimArgs sim_args(const CatCall& cc, const Chunk& c, int nq, int64_t* nodes, int* n_found, int64_t* n_calls) {
+  const cwq_index* ix = cc.ix;
+  SimArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nq = nq;
+  a.k = cc.k;
+  a.max_nodes = cc.max_nodes;
+  a.NI = ix->NI;
+  a.NL = ix->NL;
+  a.LPF = c.LPF ? c.LPF : ix->dummy;
+  a.BF = c.BF ? c.BF : ix->dummy;
+  a.ldI = std::max(ix->NI, 1);
+  a.complete = cc.complete ? 1 : 0;
+  a.int_child_begin = ix->int_child_begin;
+  a.int_child_end = ix->int_child_end;
+  a.int_nchild = ix->int_nchild;
+  a.int_bfs = ix->int_bfs;
+  a.int_has_sent = ix->int_has_sent;
+  a.int_leaf_a0 = ix->int_leaf_a0;
+  a.int_leaf_a1 = ix->int_leaf_a1;
+  a.int_leaf_b0 = ix->int_leaf_b0;
+  a.int_leaf_b1 = ix->int_leaf_b1;
+  a.row_par = ix->row_par;
+  a.row_bfs = ix->row_bfs;
+  a.row_flags = ix->row_flags;
+  a.par_int = ix->par_int;
+  a.out_nodes = nodes;
+  a.n_found = n_found;
+  a.n_calls = n_calls;
+  a.DP = ix->DP;
+  a.Mf = ix->iso_Mf;
+  a.NL_iso = ix->NL_iso;
+  a.anA = ix->an_A;
+  a.anB = ix->an_B;
+  a.ld_an = ix->ld_an;
+  a.meta = ix->row_meta;
+  a.dconst = cc.dfull;
+  return a;
+}
+
+// The three result arrays of a gathered sub-call back to the call's outputs
+int scatter_results(const CatCall& cc, SubCall& g, const int64_t* nodes2, const int* found2, const int64_t* calls2) {
+  int rc;
+  if ((rc = g.scatter(nodes2, 2 * (int64_t)cc.k, cc.nodes)) || (rc = g.scatter(found2, 1, cc.n_found))) return rc;
+  return cc.n_calls ? g.scatter(calls2, 2, cc.n_calls) : CWQ_OK;
+}
+
+// DENSE re-run of the queries `redo` (indices in the chunk at q0): the exact heap replay
+// (exact by construction), results scattered into the outputs.  By default lazily
+// (simulate_lazy_kernel: a popped node's leaf rows scored when their parent is popped);
+// CWQ_CAT_LAZY=0: every leaf row materialised first by the exact scan.
+int dense_rerun(CatCall& cc, int64_t q0, const std::vector<int>& redo) {
+  cwq_index* ix = cc.ix;
+  hipStream_t s = cc.s;
+  const int k = cc.k;
+  int rc;
+  ix->cat_tail_done = false;   // the re-run writes after the last flag gather
+  const bool lazy = !env_off("CWQ_CAT_LAZY") && ix->DP <= 2048;
+  const int64_t ldL = lazy ? 1 : std::max(ix->NL, 1);
+  const int64_t cap_dense = cc.cap_dense;
+  const size_t per_q = (size_t)ix->DP * 4 + 4 * (size_t)std::max(ix->NI, 1) * 4 + (size_t)ldL * 4 +
+                       (size_t)cap_dense * 16 + 64 + (size_t)k * 8 + (size_t)ix->D * 4;
+  const int64_t sub = std::max<int64_t>(1, std::min<int64_t>((int64_t)redo.size(), ((size_t)2 << 30) / per_q));
+  for (size_t r0 = 0; r0 < redo.size(); r0 += sub) {
+    const int ns = (int)std::min<int64_t>(sub, (int64_t)redo.size() - (int64_t)r0);
+    const int64_t ns_pad = round_up(ns, kQPad);
+    // per hard query: dense keys, heap, then status / nodes[k] / found / calls
+    if ((rc = ix->reserve(chunk_bytes(ix, ns_pad) +
+                          (size_t)ns_pad * ((size_t)ldL * 4 + cap_dense * 16 + 64 + (size_t)k * 8) + 16 * 256 +
+                          (size_t)ns_pad * ix->D * 4)))
+      return rc;
+    Bump b2(ix->ws.p, ix->ws.size);
+    Chunk c2;
+    carve_chunk(ix, b2, c2, ns);
+    float* qsub = b2.take<float>((size_t)ns * ix->D);
+    float* dense = b2.take<float>((size_t)ns_pad * ldL);
+    HeapEnt* heap2 = b2.take<HeapEnt>((size_t)ns_pad * cap_dense);
+    int* status2 = b2.take<int>(ns_pad);
+    int64_t* nodes2 = b2.take<int64_t>((size_t)ns_pad * k);
+    int* found2 = b2.take<int>(ns_pad);
+    int64_t* calls2 = b2.take<int64_t>(ns_pad);
+    std::vector<int64_t> gq(ns);   // the hard queries' indices in the call
+    for (int i = 0; i < ns; ++i) gq[i] = q0 + redo[r0 + i];
+    SubCall g;
+    if ((rc = ix->fb.reserve((size_t)ns * 8, ix->busy())) || (rc = g.open(gq, ix->fb.as<int64_t>(), s)) ||
+        (rc = g.gather(cc.q, ix->D, qsub)))
+      return rc;
+    HIPCHK(launch_pad_queries(qsub, ns, ix->D, c2.X, c2.nq_pad, ix->DP, s));
+    if ((rc = run_internal(ix, c2, s))) return rc;
+    if (!lazy && (rc = run_leaf_scan(ix, c2, EPI_KEY, true, 16, cc.dfull, dense, ix->NL, nullptr, nullptr, nullptr, 1,
+                                     nullptr, s)))
+      return rc;
+    SimArgs sd = sim_args(cc, c2, ns, nodes2, found2, calls2);   // R 0; every hard query replays (status2 is fresh scratch)
+    sd.dense_lpf = dense;
+    sd.ldL = ldL;
+    sd.heap = heap2;
+    sd.heap_cap = cap_dense;
+    sd.status = status2;
+    if (lazy) {
+      sd.X = c2.X;
+      // the run-merge replay in LDS; a query that overflows its arena is re-run on the
+      // global heap (status 1 gates it; the second kernel writes status 0)
+      if (!env_off("CWQ_CAT_LAZY_RUNS")) {
         HIPCHK(launch_simulate_lazy_runs(sd, s));
         sd.pre_status = 1;
-        HIPCHK(launch_simulate_lazy(sd, s));
-        ix->stats[4] += nqc;
-        ix->lazy_stats[0] += nqc;
-        continue;
       }
-      // a batch: the run-merge replays side by side; a query that overflows its arena goes
-      // to the DENSE re-run (its heap memory only for those)
-      HIPCHK(launch_simulate_lazy_runs(sd, s));
-      std::vector<int> hst(nqc);
-      HIPCHK(hipMemcpyAsync(hst.data(), status, (size_t)nqc * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      std::vector<int> redo;
-      for (int i = 0; i < nqc; ++i)
-        if (hst[i]) redo.push_back(i);
-      ix->stats[4] += nqc - (int64_t)redo.size();
-      ix->lazy_stats[0] += nqc - (int64_t)redo.size();
-      ix->stats[1] += (int64_t)redo.size();
-      if (!redo.empty() && (rc = dense_rerun(redo))) return rc;
-      continue;
+      HIPCHK(launch_simulate_lazy(sd, s));
+      ix->lazy_stats[1] += ns;
+    } else {
+      HIPCHK(launch_simulate(sd, s));
     }
-    if (filt && (rc = group_tables(ix, c, q + q0 * ix->D, true, s))) return rc;
-    int nst = 0;
-    std::vector<char> fbad(nqc, 0);
-    int* okf_d = nullptr;   // filter: per-query list-certified flags
-    std::vector<int> okh(filt ? nqc : 0);
-    if (filt && scat) {
-      // anisotropic rows: the exact scan into slots 1..; isotropic rows: the stream filter
-      // with the categorize key -> exact keys in list slot 0
-      if ((rc = run_leaf_scan(ix, c, EPI_TOPK, true, kl, dfull, nullptr, 0, pkey, paux, prow, R, &nst, s, 2, 1, slabs)))
-        return rc;
-      okf_d = b.take<int>((size_t)nq_pad);
-      // no anisotropic rows (nst == 1): the rerank writes list 1 itself, no merge launch
-      if ((rc = nst == 1 ? stream_cat_list(ix, c, q + q0 * ix->D, nqc, R, c.BF, dfull, okey, oaux, orow, R, okf_d, b, s)
-                         : stream_cat_list(ix, c, q + q0 * ix->D, nqc, R, c.BF, dfull, pkey, paux, prow,
-                                           (int64_t)nst * R, okf_d, b, s)))
-        return rc;
-    } else if (filt) {
-      // isotropic rows: the filter with the categorize key -> exact keys in list slot 0;
-      // anisotropic rows: the exact scan into slots 1..
-      IsoFilter fo;
-      if ((rc = run_iso_filter(ix, c, q + q0 * ix->D, nqf, R, true, false, b, fo, s))) return rc;
-      if ((rc = run_leaf_scan(ix, c, EPI_TOPK, true, kl, dfull, nullptr, 0, pkey, paux, prow, R, &nst, s, 2, 1, slabs)))
-        return rc;
-      HIPCHK(launch_final(c.X, ix->iso_Mf, ix->DP, nqc, R, kFgCapQ, fo.qcnt, fo.qover, fo.crow, fo.cu, fo.cl,
-                          fo.tl + (R - 1), 64, ix->row_meta, ix->row_par, c.BF ? c.BF : ix->dummy, std::max(ix->NI, 1), 0,
-                          pkey, paux, prow, (int64_t)nst * R, fo.okf, fo.nex, fo.tlk, fo.tr, fo.tdone, nullptr, 1, dfull,
-                          s));
-      okf_d = fo.okf;
-    } else if ((rc = run_leaf_scan(ix, c, EPI_TOPK, true, kl, dfull, nullptr, 0, pkey, paux, prow, R, &nst, s, 3, 0, slabs))) {
-      return rc;
-    }
-    if (!(filt && scat && nst == 1)) HIPCHK(launch_merge(pkey, paux, prow, nqc, nst * R, R, okey, oaux, orow, s, true));
-    SimArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.nq = nqc;
-    sa.k = k;
-    sa.R = R;
-    sa.max_nodes = max_nodes;
-    sa.NI = ix->NI;
-    sa.NL = ix->NL;
-    sa.LPF = c.LPF ? c.LPF : ix->dummy;
-    sa.BF = c.BF ? c.BF : ix->dummy;
-    sa.ldI = std::max(ix->NI, 1);
-    sa.lkey = okey;
-    sa.laux = oaux;
-    sa.lrow = orow;
-    sa.complete = complete ? 1 : 0;
-    sa.int_child_begin = ix->int_child_begin;
-    sa.int_child_end = ix->int_child_end;
-    sa.int_nchild = ix->int_nchild;
-    sa.int_bfs = ix->int_bfs;
-    sa.int_has_sent = ix->int_has_sent;
-    sa.int_leaf_a0 = ix->int_leaf_a0;
-    sa.int_leaf_a1 = ix->int_leaf_a1;
-    sa.int_leaf_b0 = ix->int_leaf_b0;
-    sa.int_leaf_b1 = ix->int_leaf_b1;
-    sa.row_par = ix->row_par;
-    sa.row_bfs = ix->row_bfs;
-    sa.row_flags = ix->row_flags;
-    sa.heap = heap;
-    sa.heap_cap = cap_list;
-    sa.out_nodes = nodes + q0 * k;
-    sa.n_found = n_found + q0;
-    sa.n_calls = n_calls ? n_calls + q0 : nullptr;
-    sa.status = status;
-    sa.par_int = ix->par_int;
-    // the pop sequence by counting over the bottleneck order (cat_count_kernel); the
-    // queries it cannot certify go through the heap replay (CWQ_CAT_COUNT=0: replay all)
-    const char* cce = getenv("CWQ_CAT_COUNT");
-    const int ccv = cce && *cce ? atoi(cce) : 1;   // 0: never, 2: always (tests)
-    const bool by_count = ix->NI > 0 && !ix->any_int_sent && ccv != 0 &&
-                          (ccv == 2 || ix->cat_count_idle < 8 || ix->cat_count_idle % kCatCountRetry == 0);
-    if (by_count) {
-      HIPCHK(launch_cat_count(sa, s));
-      sa.pre_status = 1;
-    }
-    // the count pass's status, kept on the device for the one read-back below
-    int* cst_d = by_count ? b.take<int>((size_t)nq_pad) : nullptr;
-    if (by_count) HIPCHK(hipMemcpyAsync(cst_d, status, nqc * sizeof(int), hipMemcpyDeviceToDevice, s));
-    if (okf_d) {
-      // queries whose filter lists overflowed have no list (every entry -inf, which the
-      // replay would read as "every leaf listed" and search the whole tree for: 117 ms of a
-      // 142 ms C2 batch for 4 such queries); they are re-run whole below, so skip them
-      HIPCHK(launch_skip_failed(status, okf_d, nqc, by_count ? 0 : 1, s));
-      sa.pre_status = 1;
-    }
-    HIPCHK(launch_simulate(sa, s));
-    // Two-level replay (simulate_two_kernel, §4.7) of the queries whose top-R list ended
-    // inside a tie: a second exact leaf scan keyed by the second-level bottleneck, then
-    // the replay on both lists; what it cannot certify goes to the DENSE re-run below.
-    const char* tle = getenv("CWQ_CAT_TWO");
-    const bool two = ix->NI > 0 && !ix->any_int_sent && !complete && R == 64 && !(tle && *tle && atoi(tle) == 0);
-    // the replay on the chunk itself -- its BF / LPF, the group term tables and list 1 (okey)
-    // stay on the device; list 2 by the stream filter keyed by T2 (plus the anisotropic
-    // rows' exact scan); results straight into the outputs.  gate: the first replay's
-    // status (queries it resolved are skipped)
-    int* status2 = nullptr;
-    int* okf2 = nullptr;
-    auto two_chunk = [&](const int* gate) -> int {
-      const size_t ldI = (size_t)std::max(ix->NI, 1);
-      float* T2 = b.take<float>((size_t)nq_pad * ldI);
-      float* pk2 = b.take<float>((size_t)nq_pad * slabs * R);
-      float* pa2 = b.take<float>((size_t)nq_pad * slabs * R);
-      int* pr2 = b.take<int>((size_t)nq_pad * slabs * R);
-      float* l2k = b.take<float>((size_t)nq_pad * R);
-      float* l2a = b.take<float>((size_t)nq_pad * R);
-      int* l2r = b.take<int>((size_t)nq_pad * R);
-      HeapEnt* heap2 = b.take<HeapEnt>((size_t)nq_pad * cap2);
-      status2 = b.take<int>((size_t)nq_pad);
-      okf2 = scat ? b.take<int>((size_t)nq_pad) : nullptr;   // (the exact scan's lists are certified)
-      HIPCHK(launch_cat_t2(c.BF, c.LPF, (int64_t)ldI, ix->NI, nqc, ix->par_int, okey, R, T2, s));
-      Chunk c2t = c;
-      c2t.BF = T2;   // the categorize key reads min(T2[parent], lp)
-      int nst2 = 0;
-      int rc2;
-      if (!scat) {   // both segments by the exact scan
-        if ((rc2 = run_leaf_scan(ix, c2t, EPI_TOPK, true, kl, dfull, nullptr, 0, pk2, pa2, pr2, R, &nst2, s, 3, 0, slabs)))
-          return rc2;
-      } else {
-        if ((rc2 = run_leaf_scan(ix, c2t, EPI_TOPK, true, kl, dfull, nullptr, 0, pk2, pa2, pr2, R, &nst2, s, 2, 1, slabs)))
-          return rc2;
-        if ((rc2 = nst2 == 1 ? stream_cat_list(ix, c2t, q + q0 * ix->D, nqc, R, T2, dfull, l2k, l2a, l2r, R, okf2, b, s)
-                             : stream_cat_list(ix, c2t, q + q0 * ix->D, nqc, R, T2, dfull, pk2, pa2, pr2,
-                                               (int64_t)nst2 * R, okf2, b, s)))
-          return rc2;
-      }
-      if (!(scat && nst2 == 1)) HIPCHK(launch_merge(pk2, pa2, pr2, nqc, nst2 * R, R, l2k, l2a, l2r, s, true));
-      SimArgs st2 = sa;
-      st2.pre_status = 0;
-      st2.lkey2 = l2k;
-      st2.laux2 = l2a;
-      st2.lrow2 = l2r;
-      st2.T2 = T2;
-      st2.heap = heap2;
-      st2.heap_cap = cap2;
-      st2.status = status2;
-      st2.gate = gate;
-      HIPCHK(launch_simulate_two(st2, s));
-      return 0;
-    };
-    // speculative: the second list goes out with the first replay, one status read-back for
-    // both (the last call needed it for every query; CWQ_CAT_SPEC=0 turns it off, =2 forces
-    // it -- tests)
-    const char* spe = getenv("CWQ_CAT_SPEC");
-    const int spv = spe && *spe ? atoi(spe) : 1;
-    const bool spec = two && (scat || small2) && spv != 0 && (ix->cat_two_spec || spv == 2);
-    if (spec && (rc = two_chunk(status))) return rc;
-    // the count status, the replay status, the filter's certified flags (and the second
-    // list's) written by one kernel into host-mapped memory: one sync, no pageable copies
-    if ((rc = ix->host_flags((size_t)5 * nqc))) return rc;
-    HIPCHK(launch_gather_flags(ix->hflags, nqc, cst_d, status, okf_d, spec ? status2 : nullptr, spec ? okf2 : nullptr, s,
-                               nodes + q0 * k, n_found + q0, k));
-    HIPCHK(hipStreamSynchronize(s));
-    const int* hf = ix->hflags;
-    std::vector<int> cst(hf, hf + (by_count ? nqc : 0)), st(hf + nqc, hf + 2 * (size_t)nqc);
-    std::vector<int> hs(spec ? hf + 3 * (size_t)nqc : hf, spec ? hf + 4 * (size_t)nqc : hf);
-    std::vector<int> ho(spec ? hf + 4 * (size_t)nqc : hf, spec ? hf + 5 * (size_t)nqc : hf);
-    if (okf_d) okh.assign(hf + 2 * (size_t)nqc, hf + 3 * (size_t)nqc);
-    for (int i = 0; i < (int)okh.size(); ++i)
-      if (!okh[i]) {
-        fbad[i] = 1;
-        fredo.push_back(q0 + i);
-      }
-    std::vector<int> redo;
-    for (int i = 0; i < nqc; ++i)
-      if (st[i] && !fbad[i]) redo.push_back(i);   // filter failures are re-run whole below
-    int n_counted = 0;
-    for (int i = 0; i < nqc; ++i) {
-      if (by_count && cst[i] == 0 && !fbad[i]) ++ix->stats[3], ++n_counted;
-      else if (!fbad[i]) ++ix->stats[4];
-    }
-    if (ccv != 0) ix->cat_count_idle = by_count && n_counted > 0 ? 0 : std::min(ix->cat_count_idle + 1, 1 << 30);
-    if ((scat || small2) && two) ix->cat_two_spec = (int)redo.size() == nqc;
-    if (redo.empty()) continue;
-
-    if (spec || (two && ((scat && (int)redo.size() == nqc) || small2))) {
-      if (!spec) {   // after the status read-back (gated: the first replay's resolved queries keep their results)
-        if ((rc = two_chunk(status))) return rc;
-        HIPCHK(launch_gather_flags(ix->hflags, nqc, status2, okf2, nullptr, nullptr, nullptr, s, nodes + q0 * k,
-                                   n_found + q0, k));
-        HIPCHK(hipStreamSynchronize(s));
-        hs.assign(ix->hflags, ix->hflags + nqc);
-        ho.assign(ix->hflags + nqc, ix->hflags + 2 * (size_t)nqc);
-      }
-      std::vector<int> left;
-      for (const int i : redo) {
-        if (hs[i] || (okf2 && !ho[i])) left.push_back(i);   // uncertified, or list 2 overflowed: DENSE
-        else ++ix->stats[5];
-      }
-      redo.swap(left);
-    } else if (two) {
-      ix->cat_tail_done = false;   // the gathered replay writes after the flag gather
-      std::vector<float> h1k((size_t)nqc * R), h1a((size_t)nqc * R);
-      std::vector<int> h1r((size_t)nqc * R);
-      HIPCHK(hipMemcpyAsync(h1k.data(), okey, h1k.size() * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(h1a.data(), oaux, h1a.size() * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(h1r.data(), orow, h1r.size() * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      std::vector<int> left;
-      const size_t per_q2 = chunk_bytes(ix, kQPad) / kQPad + (size_t)std::max(ix->NI, 1) * 4 + (size_t)cap2 * 16 +
-                            (size_t)R * 12 * 2 + 64 + (size_t)k * 8 + (size_t)ix->D * 4 +
-                            (size_t)R * 12 * (pick_nslab(ix, ix->NL_iso, 1) + pick_nslab(ix, ix->NL_an, 1) + 2) *
-                                scan_lists_per_slab(kl);
-      const int64_t sub2 = std::max<int64_t>(1, std::min<int64_t>((int64_t)redo.size(), ((size_t)2 << 30) / per_q2));
-      for (size_t r0 = 0; r0 < redo.size(); r0 += sub2) {
-        const int ns = (int)std::min<int64_t>(sub2, (int64_t)redo.size() - (int64_t)r0);
-        const int64_t ns_pad = round_up(ns, kQPad);
-        const int nqb2 = n_qblocks_for(ns, kl);
-        const int slabs2 = (pick_nslab(ix, ix->NL_iso, nqb2) + pick_nslab(ix, ix->NL_an, nqb2) + 2) *
-                           scan_lists_per_slab(kl);
-        const size_t ldI = (size_t)std::max(ix->NI, 1);
-        if ((rc = ix->reserve(chunk_bytes(ix, ns_pad) +
-                              (size_t)ns_pad * (ldI * 4 + (size_t)slabs2 * R * 12 + (size_t)R * 24 + cap2 * 16 + 64 +
-                                                (size_t)k * 8) +
-                              (size_t)ns * ix->D * 4 + 24 * 256)))
-          return rc;
-        Bump b2(ix->ws, ix->ws_size);
-        Chunk c2;
-        carve_chunk(ix, b2, c2, ns);
-        float* qsub = b2.take<float>((size_t)ns * ix->D);
-        float* T2 = b2.take<float>((size_t)ns_pad * ldI);
-        float* pk2 = b2.take<float>((size_t)ns_pad * slabs2 * R);
-        float* pa2 = b2.take<float>((size_t)ns_pad * slabs2 * R);
-        int* pr2 = b2.take<int>((size_t)ns_pad * slabs2 * R);
-        float* l1k = b2.take<float>((size_t)ns_pad * R);
-        float* l1a = b2.take<float>((size_t)ns_pad * R);
-        int* l1r = b2.take<int>((size_t)ns_pad * R);
-        float* l2k = b2.take<float>((size_t)ns_pad * R);
-        float* l2a = b2.take<float>((size_t)ns_pad * R);
-        int* l2r = b2.take<int>((size_t)ns_pad * R);
-        HeapEnt* heap2 = b2.take<HeapEnt>((size_t)ns_pad * cap2);
-        int* status2 = b2.take<int>(ns_pad);
-        int64_t* nodes2 = b2.take<int64_t>((size_t)ns_pad * k);
-        int* found2 = b2.take<int>(ns_pad);
-        int64_t* calls2 = b2.take<int64_t>(ns_pad);
-        std::vector<int64_t> gq(ns);
-        std::vector<float> s1k((size_t)ns * R), s1a((size_t)ns * R);
-        std::vector<int> s1r((size_t)ns * R);
-        for (int i = 0; i < ns; ++i) {
-          const int li = redo[r0 + i];
-          gq[i] = q0 + li;
-          std::copy(h1k.begin() + (size_t)li * R, h1k.begin() + (size_t)(li + 1) * R, s1k.begin() + (size_t)i * R);
-          std::copy(h1a.begin() + (size_t)li * R, h1a.begin() + (size_t)(li + 1) * R, s1a.begin() + (size_t)i * R);
-          std::copy(h1r.begin() + (size_t)li * R, h1r.begin() + (size_t)(li + 1) * R, s1r.begin() + (size_t)i * R);
-        }
-        if ((rc = ix->reserve_fb((size_t)ns * 8))) return rc;
-        int64_t* d_gq = (int64_t*)ix->fb;
-        HIPCHK(hipMemcpyAsync(d_gq, gq.data(), (size_t)ns * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(l1k, s1k.data(), s1k.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(l1a, s1a.data(), s1a.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(l1r, s1r.data(), s1r.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(launch_copy_rows(q, ix->D, d_gq, qsub, ix->D, nullptr, ns, ix->D, s));
-        HIPCHK(launch_pad_queries(qsub, ns, ix->D, c2.X, c2.nq_pad, ix->DP, s));
-        if ((rc = run_internal(ix, c2, s))) return rc;
-        HIPCHK(launch_cat_t2(c2.BF, c2.LPF, (int64_t)ldI, ix->NI, ns, ix->par_int, l1k, R, T2, s));
-        Chunk c2t = c2;
-        c2t.BF = T2;   // the leaf scan's categorize key reads min(T2[parent], lp)
-        int nst2 = 0;
-        if ((rc = run_leaf_scan(ix, c2t, EPI_TOPK, true, kl, dfull, nullptr, 0, pk2, pa2, pr2, R, &nst2, s, 3, 0,
-                                slabs2)))
-          return rc;
-        HIPCHK(launch_merge(pk2, pa2, pr2, ns, nst2 * R, R, l2k, l2a, l2r, s, true));
-        SimArgs st = sa;
-        st.nq = ns;
-        st.pre_status = 0;
-        st.LPF = c2.LPF;
-        st.BF = c2.BF;
-        st.lkey = l1k;
-        st.laux = l1a;
-        st.lrow = l1r;
-        st.lkey2 = l2k;
-        st.laux2 = l2a;
-        st.lrow2 = l2r;
-        st.T2 = T2;
-        st.heap = heap2;
-        st.heap_cap = cap2;
-        st.out_nodes = nodes2;
-        st.n_found = found2;
-        st.n_calls = calls2;
-        st.status = status2;
-        HIPCHK(launch_simulate_two(st, s));
-        // every result goes back; the uncertified ones are overwritten by the DENSE re-run
-        HIPCHK(launch_copy_rows(nodes2, 2 * (int64_t)k, nullptr, nodes, 2 * (int64_t)k, d_gq, ns, 2 * (int64_t)k, s));
-        HIPCHK(launch_copy_rows(found2, 1, nullptr, n_found, 1, d_gq, ns, 1, s));
-        if (n_calls) HIPCHK(launch_copy_rows(calls2, 2, nullptr, n_calls, 2, d_gq, ns, 2, s));
-        std::vector<int> hs(ns);
-        HIPCHK(hipMemcpyAsync(hs.data(), status2, (size_t)ns * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));   // the pageable host sources must outlive their uploads
-        for (int i = 0; i < ns; ++i) {
-          if (hs[i]) left.push_back(redo[r0 + i]);
-          else ++ix->stats[5];
-        }
-      }
-      redo.swap(left);
-    }
-    ix->stats[1] += (int64_t)redo.size();
-    n_dense_call += (int64_t)redo.size();
-    if (redo.empty()) continue;
-    if ((rc = dense_rerun(redo))) return rc;
-  }
-  if (measure && !direct) ix->cat_dense_seen = n_dense_call > 0 ? kCatDenseMemory : std::max(0, ix->cat_dense_seen - 1);
-  ix->stats[2] += (int64_t)fredo.size();
-  if (!fredo.empty()) {
-    // filter overflow: those queries through the exact path, results scattered back
-    const int64_t n = (int64_t)fredo.size();
-    const size_t D = (size_t)ix->D;
-    const size_t o_q = round_up(n * 8, 256), o_nd = o_q + round_up(n * D * 4, 256),
-                 o_f = o_nd + round_up((int64_t)n * k * 8, 256), o_c = o_f + round_up(n * 4, 256),
-                 tot = o_c + round_up(n * 8, 256);
-    if (tot > ix->fb2_size) {
-      if (ix->ws_ev_live) (void)hipEventSynchronize(ix->ws_ev);
-      if (ix->fb2) (void)hipFree(ix->fb2);
-      ix->fb2 = nullptr;
-      ix->fb2_size = 0;
-      if (hipMalloc(&ix->fb2, tot) != hipSuccess) return fail(CWQ_ERR_OOM, "categorize fallback buffers");
-      ix->fb2_size = tot;
-    }
-    char* f = (char*)ix->fb2;
-    int64_t* d_idx = (int64_t*)f;
-    float* qs = (float*)(f + o_q);
-    int64_t* nd = (int64_t*)(f + o_nd);
-    int* fd = (int*)(f + o_f);
-    int64_t* cl = (int64_t*)(f + o_c);
-    HIPCHK(hipMemcpyAsync(d_idx, fredo.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(launch_copy_rows(q, (int64_t)D, d_idx, qs, (int64_t)D, nullptr, n, (int64_t)D, s));
-    if ((rc = categorize_impl(ix, qs, n, k, max_nodes, nd, fd, cl, s, false))) return rc;
-    HIPCHK(launch_copy_rows(nd, 2 * (int64_t)k, nullptr, nodes, 2 * (int64_t)k, d_idx, n, 2 * (int64_t)k, s));
-    HIPCHK(launch_copy_rows(fd, 1, nullptr, n_found, 1, d_idx, n, 1, s));
-    if (n_calls) HIPCHK(launch_copy_rows(cl, 2, nullptr, n_calls, 2, d_idx, n, 2, s));
-    HIPCHK(hipStreamSynchronize(s));
-    ix->cat_tail_done = false;
-  }
-  if (measure) {   // the path's per-query wall time, completed (the caller syncs after a small call anyway)
-    HIPCHK(hipStreamSynchronize(s));
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count() /
-                      (double)nq;
-    double& ema = direct ? ix->cat_ema_direct[pk] : ix->cat_ema_list[pk];
-    ema = ema < 0.0 ? us : 0.75 * ema + 0.25 * us;
-    ix->cat_pref_direct[pk] = ix->cat_ema_direct[pk] >= 0.0 && ix->cat_ema_list[pk] >= 0.0 &&
-                              ix->cat_ema_direct[pk] < ix->cat_ema_list[pk];
+    if ((rc = scatter_results(cc, g, nodes2, found2, calls2)) || (rc = g.close())) return rc;
   }
   return CWQ_OK;
 }
+
+// One chunk of a call in the workspace.
+struct CatChunk {
+  Bump b;
+  int64_t q0 = 0;
+  int nqc = 0;
+  int64_t nq_pad = 0;
+  int slabs = 0;
+  Chunk c;
+  const float* qc = nullptr;                                 // its queries
+  float *pkey = nullptr, *paux = nullptr, *okey = nullptr, *oaux = nullptr;   // partial lists [slabs], list 1
+  int *prow = nullptr, *orow = nullptr;
+  int* status = nullptr;
+  int64_t* nodes = nullptr;                                  // its outputs
+  int* n_found = nullptr;
+  int64_t* n_calls = nullptr;
+};
+
+// The chunk's queries straight through the exact lazy replay: every pushed entry scored when
+// its parent is popped.
+int direct_chunk(CatCall& cc, CatChunk& ch) {
+  cwq_index* ix = cc.ix;
+  hipStream_t s = cc.s;
+  const int nqc = ch.nqc;
+  int rc;
+  SimArgs sd = sim_args(cc, ch.c, nqc, ch.nodes, ch.n_found, ch.n_calls);
+  sd.status = ch.status;
+  sd.X = ch.c.X;
+  ix->cat_tail_done = false;
+  if (cc.pk == 0) {   // a few queries: the global-heap form queued behind for arena overflows
+    sd.heap = ch.b.take<HeapEnt>((size_t)ch.nq_pad * cc.cap_dense);
+    sd.heap_cap = cc.cap_dense;
+    HIPCHK(launch_simulate_lazy_runs(sd, s));
+    sd.pre_status = 1;
+    HIPCHK(launch_simulate_lazy(sd, s));
+    ix->stats[4] += nqc;
+    ix->lazy_stats[0] += nqc;
+    return CWQ_OK;
+  }
+  // a batch: the run-merge replays side by side; a query that overflows its arena goes
+  // to the DENSE re-run (its heap memory only for those)
+  HIPCHK(launch_simulate_lazy_runs(sd, s));
+  std::vector<int> hst(nqc);
+  HIPCHK(hipMemcpyAsync(hst.data(), ch.status, (size_t)nqc * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::vector<int> redo;
+  for (int i = 0; i < nqc; ++i)
+    if (hst[i]) redo.push_back(i);
+  ix->stats[4] += nqc - (int64_t)redo.size();
+  ix->lazy_stats[0] += nqc - (int64_t)redo.size();
+  ix->stats[1] += (int64_t)redo.size();
+  if (!redo.empty() && (rc = dense_rerun(cc, ch.q0, redo))) return rc;
+  return CWQ_OK;
+}
+
+// List 1 of the chunk, the top-R leaf rows by the categorize key min(BF[parent], lp), into
+// okey / oaux / orow.  okf_d: the filter's per-query list-certified flags (none: exact scan).
+int first_list(CatCall& cc, CatChunk& ch, int** okf_d) {
+  cwq_index* ix = cc.ix;
+  hipStream_t s = cc.s;
+  const int R = cc.R, nqc = ch.nqc, slabs = ch.slabs;
+  Chunk& c = ch.c;
+  Bump& b = ch.b;
+  int rc, nst = 0;
+  *okf_d = nullptr;
+  if (cc.filt && cc.scat) {
+    // anisotropic rows: the exact scan into slots 1..; isotropic rows: the stream filter
+    // with the categorize key -> exact keys in list slot 0
+    if ((rc = run_leaf_scan(ix, c, EPI_TOPK, true, kl, cc.dfull, nullptr, 0, ch.pkey, ch.paux, ch.prow, R, &nst, s, 2, 1,
+                            slabs)))
+      return rc;
+    *okf_d = b.take<int>((size_t)ch.nq_pad);
+    // no anisotropic rows (nst == 1): the rerank writes list 1 itself, no merge launch
+    if ((rc = nst == 1 ? stream_cat_list(ix, c, ch.qc, nqc, R, c.BF, cc.dfull, ch.okey, ch.oaux, ch.orow, R, *okf_d, b, s)
+                       : stream_cat_list(ix, c, ch.qc, nqc, R, c.BF, cc.dfull, ch.pkey, ch.paux, ch.prow,
+                                         (int64_t)nst * R, *okf_d, b, s)))
+      return rc;
+  } else if (cc.filt) {
+    // isotropic rows: the filter with the categorize key -> exact keys in list slot 0;
+    // anisotropic rows: the exact scan into slots 1..
+    IsoFilter fo;
+    if ((rc = run_iso_filter(ix, c, ch.qc, round_up(nqc, kFgTile), R, true, false, b, fo, s))) return rc;
+    if ((rc = run_leaf_scan(ix, c, EPI_TOPK, true, kl, cc.dfull, nullptr, 0, ch.pkey, ch.paux, ch.prow, R, &nst, s, 2, 1,
+                            slabs)))
+      return rc;
+    HIPCHK(launch_final(c.X, ix->iso_Mf, ix->DP, nqc, R, kFgCapQ, fo.qcnt, fo.qover, fo.crow, fo.cu, fo.cl,
+                        fo.tl + (R - 1), 64, ix->row_meta, ix->row_par, c.BF ? c.BF : ix->dummy, std::max(ix->NI, 1), 0,
+                        ch.pkey, ch.paux, ch.prow, (int64_t)nst * R, fo.okf, fo.nex, fo.tlk, fo.tr, fo.tdone, nullptr, 1,
+                        cc.dfull, s));
+    *okf_d = fo.okf;
+  } else if ((rc = run_leaf_scan(ix, c, EPI_TOPK, true, kl, cc.dfull, nullptr, 0, ch.pkey, ch.paux, ch.prow, R, &nst, s, 3,
+                                 0, slabs))) {
+    return rc;
+  }
+  if (!(cc.filt && cc.scat && nst == 1))
+    HIPCHK(launch_merge(ch.pkey, ch.paux, ch.prow, nqc, nst * R, R, ch.okey, ch.oaux, ch.orow, s, true));
+  return CWQ_OK;
+}
+
+// Two-level replay (simulate_two_kernel, §4.7) of the queries of chunk c (qc) whose top-R list
+// ended inside a tie: the second-level table T2 from list 1 (st.lkey), a second leaf scan keyed
+// by it -- by the stream filter (stream: plus the anisotropic rows' exact scan) or the exact
+// scan of every row -- the merge, and the replay on both lists.  st: the replay arguments with
+// list 1 and the outputs; gate: queries with gate[q] == 0 are skipped (none: null).  Scratch
+// from b; status2 / okf2: the replay's status and (stream) list 2's certified flags.
+int two_level(const CatCall& cc, const Chunk& c, const float* qc, int slabs, bool stream, SimArgs st, const int* gate,
+              Bump& b, int** status2, int** okf2) {
+  cwq_index* ix = cc.ix;
+  hipStream_t s = cc.s;
+  const int R = cc.R, nq = st.nq;
+  const int64_t nq_pad = c.nq_pad;
+  const size_t ldI = (size_t)std::max(ix->NI, 1);
+  float* T2 = b.take<float>((size_t)nq_pad * ldI);
+  float* pk2 = b.take<float>((size_t)nq_pad * slabs * R);
+  float* pa2 = b.take<float>((size_t)nq_pad * slabs * R);
+  int* pr2 = b.take<int>((size_t)nq_pad * slabs * R);
+  float* l2k = b.take<float>((size_t)nq_pad * R);
+  float* l2a = b.take<float>((size_t)nq_pad * R);
+  int* l2r = b.take<int>((size_t)nq_pad * R);
+  HeapEnt* heap2 = b.take<HeapEnt>((size_t)nq_pad * cc.cap2);
+  *status2 = b.take<int>((size_t)nq_pad);
+  *okf2 = stream ? b.take<int>((size_t)nq_pad) : nullptr;   // (the exact scan's lists are certified)
+  HIPCHK(launch_cat_t2(c.BF, c.LPF, (int64_t)ldI, ix->NI, nq, ix->par_int, st.lkey, R, T2, s));
+  Chunk c2t = c;
+  c2t.BF = T2;   // the categorize key reads min(T2[parent], lp)
+  int nst2 = 0;
+  int rc;
+  if (!stream) {   // both segments by the exact scan
+    if ((rc = run_leaf_scan(ix, c2t, EPI_TOPK, true, kl, cc.dfull, nullptr, 0, pk2, pa2, pr2, R, &nst2, s, 3, 0, slabs)))
+      return rc;
+  } else {
+    if ((rc = run_leaf_scan(ix, c2t, EPI_TOPK, true, kl, cc.dfull, nullptr, 0, pk2, pa2, pr2, R, &nst2, s, 2, 1, slabs)))
+      return rc;
+    if ((rc = nst2 == 1 ? stream_cat_list(ix, c2t, qc, nq, R, T2, cc.dfull, l2k, l2a, l2r, R, *okf2, b, s)
+                        : stream_cat_list(ix, c2t, qc, nq, R, T2, cc.dfull, pk2, pa2, pr2, (int64_t)nst2 * R, *okf2, b,
+                                          s)))
+      return rc;
+  }
+  if (!(stream && nst2 == 1)) HIPCHK(launch_merge(pk2, pa2, pr2, nq, nst2 * R, R, l2k, l2a, l2r, s, true));
+  st.pre_status = 0;
+  st.lkey2 = l2k;
+  st.laux2 = l2a;
+  st.lrow2 = l2r;
+  st.T2 = T2;
+  st.heap = heap2;
+  st.heap_cap = cc.cap2;
+  st.status = *status2;
+  st.gate = gate;
+  HIPCHK(launch_simulate_two(st, s));
+  return CWQ_OK;
+}
+
+// The two-level replay of the chunk's queries `redo` gathered into chunks of their own (list 1
+// through the host, the internal pass recomputed); left: those it could not certify.
+int two_level_gathered(CatCall& cc, CatChunk& ch, const std::vector<int>& redo, std::vector<int>& left) {
+  cwq_index* ix = cc.ix;
+  hipStream_t s = cc.s;
+  const int R = cc.R, k = cc.k, nqc = ch.nqc;
+  const int64_t cap2 = cc.cap2;
+  int rc;
+  ix->cat_tail_done = false;   // the gathered replay writes after the flag gather
+  std::vector<float> h1k((size_t)nqc * R), h1a((size_t)nqc * R);
+  std::vector<int> h1r((size_t)nqc * R);
+  HIPCHK(hipMemcpyAsync(h1k.data(), ch.okey, h1k.size() * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h1a.data(), ch.oaux, h1a.size() * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h1r.data(), ch.orow, h1r.size() * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const size_t per_q2 = chunk_bytes(ix, kQPad) / kQPad + (size_t)std::max(ix->NI, 1) * 4 + (size_t)cap2 * 16 +
+                        (size_t)R * 12 * 2 + 64 + (size_t)k * 8 + (size_t)ix->D * 4 +
+                        (size_t)R * 12 * (pick_nslab(ix, ix->NL_iso, 1) + pick_nslab(ix, ix->NL_an, 1) + 2) *
+                            scan_lists_per_slab(kl);
+  const int64_t sub2 = std::max<int64_t>(1, std::min<int64_t>((int64_t)redo.size(), ((size_t)2 << 30) / per_q2));
+  for (size_t r0 = 0; r0 < redo.size(); r0 += sub2) {
+    const int ns = (int)std::min<int64_t>(sub2, (int64_t)redo.size() - (int64_t)r0);
+    const int64_t ns_pad = round_up(ns, kQPad);
+    const int nqb2 = n_qblocks_for(ns, kl);
+    const int slabs2 = (pick_nslab(ix, ix->NL_iso, nqb2) + pick_nslab(ix, ix->NL_an, nqb2) + 2) *
+                       scan_lists_per_slab(kl);
+    const size_t ldI = (size_t)std::max(ix->NI, 1);
+    if ((rc = ix->reserve(chunk_bytes(ix, ns_pad) +
+                          (size_t)ns_pad * (ldI * 4 + (size_t)slabs2 * R * 12 + (size_t)R * 24 + cap2 * 16 + 64 +
+                                            (size_t)k * 8) +
+                          (size_t)ns * ix->D * 4 + 24 * 256)))
+      return rc;
+    Bump b2(ix->ws.p, ix->ws.size);
+    Chunk c2;
+    carve_chunk(ix, b2, c2, ns);
+    float* qsub = b2.take<float>((size_t)ns * ix->D);
+    float* l1k = b2.take<float>((size_t)ns_pad * R);
+    float* l1a = b2.take<float>((size_t)ns_pad * R);
+    int* l1r = b2.take<int>((size_t)ns_pad * R);
+    int64_t* nodes2 = b2.take<int64_t>((size_t)ns_pad * k);
+    int* found2 = b2.take<int>(ns_pad);
+    int64_t* calls2 = b2.take<int64_t>(ns_pad);
+    std::vector<int64_t> gq(ns);
+    std::vector<float> s1k((size_t)ns * R), s1a((size_t)ns * R);
+    std::vector<int> s1r((size_t)ns * R);
+    for (int i = 0; i < ns; ++i) {
+      const int li = redo[r0 + i];
+      gq[i] = ch.q0 + li;
+      std::copy(h1k.begin() + (size_t)li * R, h1k.begin() + (size_t)(li + 1) * R, s1k.begin() + (size_t)i * R);
+      std::copy(h1a.begin() + (size_t)li * R, h1a.begin() + (size_t)(li + 1) * R, s1a.begin() + (size_t)i * R);
+      std::copy(h1r.begin() + (size_t)li * R, h1r.begin() + (size_t)(li + 1) * R, s1r.begin() + (size_t)i * R);
+    }
+    SubCall g;
+    if ((rc = ix->fb.reserve((size_t)ns * 8, ix->busy())) || (rc = g.open(gq, ix->fb.as<int64_t>(), s))) return rc;
+    HIPCHK(hipMemcpyAsync(l1k, s1k.data(), s1k.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(l1a, s1a.data(), s1a.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(l1r, s1r.data(), s1r.size() * 4, hipMemcpyHostToDevice, s));
+    if ((rc = g.gather(cc.q, ix->D, qsub))) return rc;
+    HIPCHK(launch_pad_queries(qsub, ns, ix->D, c2.X, c2.nq_pad, ix->DP, s));
+    if ((rc = run_internal(ix, c2, s))) return rc;
+    SimArgs st = sim_args(cc, c2, ns, nodes2, found2, calls2);
+    st.R = R;
+    st.lkey = l1k;
+    st.laux = l1a;
+    st.lrow = l1r;
+    int *status2 = nullptr, *okf2 = nullptr;
+    if ((rc = two_level(cc, c2, qsub, slabs2, false, st, nullptr, b2, &status2, &okf2))) return rc;
+    // every result goes back; the uncertified ones are overwritten by the DENSE re-run
+    if ((rc = scatter_results(cc, g, nodes2, found2, calls2))) return rc;
+    std::vector<int> hs(ns);
+    HIPCHK(hipMemcpyAsync(hs.data(), status2, (size_t)ns * 4, hipMemcpyDeviceToHost, s));
+    if ((rc = g.close())) return rc;   // (the list sources are pageable host memory too)
+    for (int i = 0; i < ns; ++i) {
+      if (hs[i]) left.push_back(redo[r0 + i]);
+      else ++ix->stats[5];
+    }
+  }
+  return CWQ_OK;
+}
+
+// One chunk of the call: the queries [q0, q0 + cq).
+int cat_chunk(CatCall& cc, int64_t q0) {
+  cwq_index* ix = cc.ix;
+  hipStream_t s = cc.s;
+  const int R = cc.R, k = cc.k;
+  const bool filt = cc.filt, scat = cc.scat, small2 = cc.small2, direct = cc.direct;
+  int rc;
+  const int nqc = (int)std::min(cc.cq, cc.nq - q0);
+  const int64_t nq_pad = round_up(nqc, kQPad);
+  const int slabs = cc.n_slabs(n_qblocks_for(nqc, kl));
+  const int64_t nqf = round_up(nqc, kFgTile);
+  size_t need = chunk_bytes(ix, nq_pad) + (size_t)nq_pad * ((size_t)slabs * R * 12 + (size_t)R * 12 +
+                                                            (size_t)cc.cap_list * 16 + 12) + 17 * 256 +
+                (filt ? (size_t)nqf * cc.filt_q + 4096 * 8 : 0);
+  if (direct && cc.pk == 0) need += (size_t)nq_pad * ((size_t)cc.cap_dense * 16 + 16) + 2 * 256;
+  if (scat || small2)   // + the second list's stream pass, T2, lists and heap (the two-level replay in place)
+    need += (scat ? 2 * stream_cat_bytes(ix, nqc) : 0) + (size_t)nq_pad * ((size_t)std::max(ix->NI, 1) * 4 + (size_t)slabs * R * 12 +
+                                                               (size_t)R * 12 + (size_t)cc.cap2 * 16 + 16) + 32 * 256;
+  if ((rc = ix->reserve(need))) return rc;
+  CatChunk ch{Bump(ix->ws.p, ix->ws.size)};
+  Bump& b = ch.b;
+  Chunk& c = ch.c;
+  ch.q0 = q0;
+  ch.nqc = nqc;
+  ch.nq_pad = nq_pad;
+  ch.slabs = slabs;
+  ch.qc = cc.q + q0 * ix->D;
+  ch.nodes = cc.nodes + q0 * k;
+  ch.n_found = cc.n_found + q0;
+  ch.n_calls = cc.n_calls ? cc.n_calls + q0 : nullptr;
+  carve_chunk(ix, b, c, nqc);
+  ch.pkey = b.take<float>((size_t)nq_pad * slabs * R);
+  ch.paux = b.take<float>((size_t)nq_pad * slabs * R);
+  ch.prow = b.take<int>((size_t)nq_pad * slabs * R);
+  ch.okey = b.take<float>((size_t)nq_pad * R);
+  ch.oaux = b.take<float>((size_t)nq_pad * R);
+  ch.orow = b.take<int>((size_t)nq_pad * R);
+  HeapEnt* heap = b.take<HeapEnt>((size_t)nq_pad * cc.cap_list);
+  int* status = ch.status = b.take<int>((size_t)nq_pad);
+  HIPCHK(launch_pad_queries(ch.qc, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
+  if ((rc = run_internal(ix, c, s, true, ch.qc, direct ? -1 : (filt ? 1 : -1)))) return rc;
+  if (direct) return direct_chunk(cc, ch);
+  if (filt && (rc = group_tables(ix, c, ch.qc, true, s))) return rc;
+  int* okf_d = nullptr;   // filter: per-query list-certified flags
+  if ((rc = first_list(cc, ch, &okf_d))) return rc;
+  SimArgs sa = sim_args(cc, c, nqc, ch.nodes, ch.n_found, ch.n_calls);
+  sa.R = R;
+  sa.lkey = ch.okey;
+  sa.laux = ch.oaux;
+  sa.lrow = ch.orow;
+  sa.heap = heap;
+  sa.heap_cap = cc.cap_list;
+  sa.status = status;
+  // the pop sequence by counting over the bottleneck order (cat_count_kernel); the
+  // queries it cannot certify go through the heap replay (CWQ_CAT_COUNT=0: replay all;
+  // 2: always -- tests)
+  const int ccv = env_int("CWQ_CAT_COUNT", 1);
+  const bool by_count = ix->NI > 0 && !ix->any_int_sent && ccv != 0 &&
+                        (ccv == 2 || ix->cat_count_idle < 8 || ix->cat_count_idle % kCatCountRetry == 0);
+  if (by_count) {
+    HIPCHK(launch_cat_count(sa, s));
+    sa.pre_status = 1;
+  }
+  // the count pass's status, kept on the device for the one read-back below
+  int* cst_d = by_count ? b.take<int>((size_t)nq_pad) : nullptr;
+  if (by_count) HIPCHK(hipMemcpyAsync(cst_d, status, nqc * sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (okf_d) {
+    // queries whose filter lists overflowed have no list (every entry -inf, which the
+    // replay would read as "every leaf listed" and search the whole tree for: 117 ms of a
+    // 142 ms C2 batch for 4 such queries); they are re-run whole below, so skip them
+    HIPCHK(launch_skip_failed(status, okf_d, nqc, by_count ? 0 : 1, s));
+    sa.pre_status = 1;
+  }
+  HIPCHK(launch_simulate(sa, s));
+  // The two-level replay (two_level) of the queries whose list ended inside a tie; what it
+  // cannot certify goes to the DENSE re-run below.  On the chunk itself (scat / small2) its BF /
+  // LPF, the group term tables and list 1 stay on the device and the results go straight into
+  // the outputs, gated by the first replay's status (queries it resolved are skipped).
+  const bool two = ix->NI > 0 && !ix->any_int_sent && !cc.complete && R == 64 && !env_off("CWQ_CAT_TWO");
+  int *status2 = nullptr, *okf2 = nullptr;
+  // speculative: the second list goes out with the first replay, one status read-back for
+  // both (the last call needed it for every query; CWQ_CAT_SPEC=0 turns it off, =2 forces
+  // it -- tests)
+  const int spv = env_int("CWQ_CAT_SPEC", 1);
+  const bool spec = two && (scat || small2) && spv != 0 && (ix->cat_two_spec || spv == 2);
+  if (spec && (rc = two_level(cc, c, ch.qc, slabs, scat, sa, status, b, &status2, &okf2))) return rc;
+  // the count status, the replay status, the filter's certified flags (and the second
+  // list's) written by one kernel into host-mapped memory: one sync, no pageable copies
+  if ((rc = ix->hflags.reserve((size_t)5 * nqc * sizeof(int)))) return rc;
+  int* hf = ix->hflags.as<int>();
+  HIPCHK(launch_gather_flags(hf, nqc, cst_d, status, okf_d, spec ? status2 : nullptr, spec ? okf2 : nullptr, s, ch.nodes,
+                             ch.n_found, k));
+  HIPCHK(hipStreamSynchronize(s));
+  std::vector<int> cst(hf, hf + (by_count ? nqc : 0)), st(hf + nqc, hf + 2 * (size_t)nqc);
+  std::vector<int> hs(spec ? hf + 3 * (size_t)nqc : hf, spec ? hf + 4 * (size_t)nqc : hf);
+  std::vector<int> ho(spec ? hf + 4 * (size_t)nqc : hf, spec ? hf + 5 * (size_t)nqc : hf);
+  std::vector<char> fbad(nqc, 0);
+  if (okf_d)
+    for (int i = 0; i < nqc; ++i)
+      if (!hf[2 * (size_t)nqc + i]) {
+        fbad[i] = 1;
+        cc.fredo.push_back(q0 + i);
+      }
+  std::vector<int> redo;
+  for (int i = 0; i < nqc; ++i)
+    if (st[i] && !fbad[i]) redo.push_back(i);   // filter failures are re-run whole after the chunks
+  int n_counted = 0;
+  for (int i = 0; i < nqc; ++i) {
+    if (by_count && cst[i] == 0 && !fbad[i]) ++ix->stats[3], ++n_counted;
+    else if (!fbad[i]) ++ix->stats[4];
+  }
+  if (ccv != 0) ix->cat_count_idle = by_count && n_counted > 0 ? 0 : std::min(ix->cat_count_idle + 1, 1 << 30);
+  if ((scat || small2) && two) ix->cat_two_spec = (int)redo.size() == nqc;
+  if (redo.empty()) return CWQ_OK;
+
+  if (spec || (two && ((scat && (int)redo.size() == nqc) || small2))) {
+    if (!spec) {   // after the status read-back (gated: the first replay's resolved queries keep their results)
+      if ((rc = two_level(cc, c, ch.qc, slabs, scat, sa, status, b, &status2, &okf2))) return rc;
+      HIPCHK(launch_gather_flags(hf, nqc, status2, okf2, nullptr, nullptr, nullptr, s, ch.nodes, ch.n_found, k));
+      HIPCHK(hipStreamSynchronize(s));
+      hs.assign(hf, hf + nqc);
+      ho.assign(hf + nqc, hf + 2 * (size_t)nqc);
+    }
+    std::vector<int> left;
+    for (const int i : redo) {
+      if (hs[i] || (okf2 && !ho[i])) left.push_back(i);   // uncertified, or list 2 overflowed: DENSE
+      else ++ix->stats[5];
+    }
+    redo.swap(left);
+  } else if (two) {
+    std::vector<int> left;
+    if ((rc = two_level_gathered(cc, ch, redo, left))) return rc;
+    redo.swap(left);
+  }
+  ix->stats[1] += (int64_t)redo.size();
+  cc.n_dense += (int64_t)redo.size();
+  if (redo.empty()) return CWQ_OK;
+  return dense_rerun(cc, q0, redo);
+}
+
+// Filter overflow: the queries cc.fredo through the exact path, results scattered back.
+// again(queries, n, nodes, found, calls): categorize_impl on them without the filter.
+template <class F>
+int rerun_unfiltered(CatCall& cc, F again) {
+  cwq_index* ix = cc.ix;
+  hipStream_t s = cc.s;
+  const int k = cc.k;
+  const int64_t n = (int64_t)cc.fredo.size();
+  const size_t D = (size_t)ix->D;
+  const size_t o_q = round_up(n * 8, 256), o_nd = o_q + round_up(n * D * 4, 256),
+               o_f = o_nd + round_up((int64_t)n * k * 8, 256), o_c = o_f + round_up(n * 4, 256),
+               tot = o_c + round_up(n * 8, 256);
+  int rc;
+  if ((rc = ix->fb2.reserve(tot, ix->busy()))) return rc;
+  char* f = ix->fb2.as<char>();
+  float* qs = (float*)(f + o_q);
+  int64_t* nd = (int64_t*)(f + o_nd);
+  int* fd = (int*)(f + o_f);
+  int64_t* cl = (int64_t*)(f + o_c);
+  SubCall g;
+  if ((rc = g.open(cc.fredo, (int64_t*)f, s)) || (rc = g.gather(cc.q, (int64_t)D, qs))) return rc;
+  if ((rc = again(qs, n, nd, fd, cl))) return rc;
+  if ((rc = scatter_results(cc, g, nd, fd, cl)) || (rc = g.close())) return rc;
+  ix->cat_tail_done = false;
+  return CWQ_OK;
+}
+
+// cwq_categorize body.  allow_filter: the isotropic leaf rows go through the bf16-MFMA
+// filter with the categorize key (run_iso_filter, cat); queries whose candidate lists
+// overflow are re-run with allow_filter = false (the exact scan of every leaf row).
+int categorize_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t max_nodes, int64_t* nodes,
+                    int32_t* n_found, int64_t* n_calls, hipStream_t s, bool allow_filter) {
+  CatCall cc{ix, q, nq, k, max_nodes, nodes, n_found, n_calls, s};
+  cc.dfull = (float)((double)ix->D * (double)logf(2.0f * (float)M_PI));
+  const int R = cc.R = std::max(1, std::min(64, ix->NL));
+  cc.complete = ix->NL <= R;
+  cc.cap_list = 1 + (int64_t)ix->NI + R;
+  cc.cap2 = 1 + (int64_t)ix->NI + 2 * R;
+  cc.cap_dense = 1 + (int64_t)ix->NI + ix->NL;
+  // a call of a few queries takes the per-call stream lists from kStreamMinRows rows on (as
+  // Fast does): the exact 64-wide list scan of a small tree is its latency chain -- qqp1k
+  // (1,000 rows x 1,024): 285 us a list, profiles/r05_published_shapes_v4.log
+  cc.filt = allow_filter && use_filter(ix, R, nq <= 64 ? kStreamMinRows : kFiltMinRows, false) &&
+            !env_off("CWQ_CAT_FILTER");
+  cc.filt_q = cc.filt ? iso_filter_bytes_per_query(ix, (int)(ix->ld_f / kFgTile)) : 0;
+  const int max_slabs = cc.n_slabs(n_qblocks_for(nq, kl));
+  cc.cq = chunk_queries(ix, nq, (size_t)cc.cap_list * 16 + (size_t)max_slabs * R * 12 + R * 12 + cc.filt_q);
+  if (cc.filt && cc.cq < nq) cc.cq = std::max<int64_t>(kFgTile, cc.cq / kFgTile * kFgTile);   // whole query tiles
+  // a few queries (the reference's one cobweb_predict per query): the lists through the
+  // per-call stream filter (stream_cat_list), and a two-level replay of every query of the
+  // call reuses the chunk's internal pass instead of gathering and recomputing it
+  cc.scat = cc.filt && nq <= cc.cq && stream_cat_ok(ix, (int)nq, R);
+  // a few queries without the filter (small trees): the two-level replay on the chunk too,
+  // list 2 by the exact scan (instead of gathering the queries and re-running the internal
+  // pass: qqp1k's Basic call 1.02 ms, profiles/r05_published_shapes_v3.log)
+  cc.small2 = !cc.filt && nq <= std::min<int64_t>(cc.cq, 64);
+  // every query resolved in the first chunk by the list paths: the flag gathers cleared the
+  // node tails after the last results, so the caller needs no clear_tail launch / sync
+  ix->cat_tail_done = nq <= cc.cq;
+  cat_policy_begin(cc, allow_filter);
+  const auto t_call = std::chrono::steady_clock::now();
+  int rc;
+  for (int64_t q0 = 0; q0 < nq; q0 += cc.cq)
+    if ((rc = cat_chunk(cc, q0))) return rc;
+  if (cc.measure && !cc.direct)
+    ix->cat_dense_seen = cc.n_dense > 0 ? kCatDenseMemory : std::max(0, ix->cat_dense_seen - 1);
+  ix->stats[2] += (int64_t)cc.fredo.size();
+  auto again = [&](const float* qs, int64_t n, int64_t* nd, int* fd, int64_t* cl) {
+    return categorize_impl(ix, qs, n, k, max_nodes, nd, fd, cl, s, false);
+  };
+  if (!cc.fredo.empty() && (rc = rerun_unfiltered(cc, again))) return rc;
+  return cat_policy_end(cc, t_call);
+}
 }  // namespace
+
+static int cat_args(const cwq_index* ix, const float* q, int64_t nq, int32_t k, const int64_t* nodes,
+                    const int32_t* n_found) {
+  if (!ix || (!q && nq > 0) || (nq > 0 && (!nodes || !n_found))) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (k <= 0) return fail(CWQ_ERR_ARG, "k must be >= 1");
+  return CWQ_OK;
+}
+static void cat_reset(cwq_index* ix) {
+  for (int64_t& t : ix->stats) t = 0;
+  ix->lazy_stats[0] = ix->lazy_stats[1] = 0;
+}
 
 extern "C" int cwq_categorize(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t max_nodes, int64_t* nodes,
                               int32_t* n_found, int64_t* n_calls, void* stream) {
-  if (!ix || (!q && nq > 0) || (nq > 0 && (!nodes || !n_found))) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (k <= 0) return fail(CWQ_ERR_ARG, "k must be >= 1");
+  if (int rc = cat_args(ix, q, nq, k, nodes, n_found)) return rc;
   if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
-  for (int64_t& t : ix->stats) t = 0;
-  ix->lazy_stats[0] = ix->lazy_stats[1] = 0;
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  cat_reset(ix);
+  if (call.rc) return call.rc;
   const int rc = categorize_impl(ix, q, nq, k, max_nodes, nodes, n_found, n_calls, s, true);
   ix->stats[0] = nq;
   if (rc) return rc;
@@ -4190,27 +4239,20 @@ extern "C" int cwq_categorize(cwq_index* ix, const float* q, int64_t nq, int32_t
 // written by the kernels straight into mapped host memory, the call returning synchronized.
 extern "C" int cwq_categorize_host(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t max_nodes,
                                    int64_t* nodes, int32_t* n_found, int64_t* n_calls, void* stream) {
-  if (!ix || (!q && nq > 0) || (nq > 0 && (!nodes || !n_found))) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (k <= 0) return fail(CWQ_ERR_ARG, "k must be >= 1");
+  if (int rc = cat_args(ix, q, nq, k, nodes, n_found)) return rc;
   if (nq == 0) return CWQ_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DevGuard dg(ix->device);
-  for (int64_t& t : ix->stats) t = 0;
-  ix->lazy_stats[0] = ix->lazy_stats[1] = 0;
   hipStream_t s = (hipStream_t)stream;
-  WsUse wu(ix, s);
-  ScanCfgScope scs(nq);
-  if (wu.rc) return wu.rc;
+  QueryCall call(ix, nq, s);
+  cat_reset(ix);
+  if (call.rc) return call.rc;
   const size_t qb = (size_t)nq * ix->D * 4, nb = (size_t)round_up(nq * k * 8, 256), cb = (size_t)round_up(nq * 8, 256),
                fb = (size_t)nq * 4;
   int rc;
-  if ((rc = ix->host_io(qb, nb + cb + fb))) return rc;
-  memcpy(ix->hq, q, qb);
-  HIPCHK(hipMemcpyAsync(ix->dq, ix->hq, qb, hipMemcpyHostToDevice, s));
-  int64_t* hn = (int64_t*)ix->hout;
-  int64_t* hc = (int64_t*)((char*)ix->hout + nb);
-  int32_t* hf = (int32_t*)((char*)ix->hout + nb + cb);
-  rc = categorize_impl(ix, (const float*)ix->dq, nq, k, max_nodes, hn, hf, hc, s, true);
+  if ((rc = stage_host(ix, q, qb, nb + cb + fb, s))) return rc;
+  int64_t* hn = ix->hout.as<int64_t>();
+  int64_t* hc = (int64_t*)(ix->hout.as<char>() + nb);
+  int32_t* hf = (int32_t*)(ix->hout.as<char>() + nb + cb);
+  rc = categorize_impl(ix, ix->dq.as<float>(), nq, k, max_nodes, hn, hf, hc, s, true);
   ix->stats[0] = nq;
   if (rc) return rc;
   if (!ix->cat_tail_done) {   // (otherwise categorize_impl's last sync already covers every write)

@@ -15,6 +15,15 @@ by spaces when knobs contain commas: pass --libs once per arm).
 
 --rank-ce times cwq_rank_ce with its gradient instead (HIP events, the arms taking turns inside
 every repetition) and checks that the arms return the same bits.
+
+    python scripts/ab_libs.py --libs a.so,b.so --clusters 100 --categorize 1,64,1024
+
+--categorize times Basic (categorize) on the list paths (CWQ_CAT_DIRECT=0): host wall time of
+the call plus a device synchronize (time.perf_counter, not HIP events), the arms taking turns
+inside every repetition, and checks that the arms return the same nodes, found counts and call
+counts.  The query counts run in the order given on each arm's one index, so the handle's
+categorize policy state (cat_two_spec, cat_count_idle) carries from one count to the next --
+the same sequence in every arm.
 """
 import argparse
 import contextlib
@@ -68,6 +77,29 @@ def rank_ce_ab(paths, arms, Q, nqs, reps):
                   f"{'same bits' if same else 'MISMATCH'}", flush=True)
 
 
+def categorize_ab(paths, arms, Q, nqs, reps, k):
+    """Basic (categorize) per arm, the arms taking turns inside every repetition (host wall time
+    of the call plus a synchronize); nodes, found and calls must be equal between the arms.  CWQ_CAT_DIRECT=0 as in the tests: the path choice is
+    measured at run time otherwise, and the arms could take different paths."""
+    with env({"CWQ_CAT_DIRECT": "0"}):
+        for nq in nqs:
+            q = Q[:nq].contiguous()
+            outs = [ix.categorize(q, k, 100000) for ix in arms]
+            same = all(torch.equal(a, b) for o in outs[1:] for a, b in zip(o, outs[0]))
+            torch.cuda.synchronize()
+            ts = [[] for _ in arms]
+            for _ in range(reps):
+                for i, ix in enumerate(arms):
+                    t0 = time.perf_counter()
+                    ix.categorize(q, k, 100000)
+                    torch.cuda.synchronize()
+                    ts[i].append((time.perf_counter() - t0) * 1e3)
+            med = [statistics.median(t) for t in ts]
+            for p, t, m in zip(paths, ts, med):
+                print(f"categorize nq={nq} {os.path.basename(p)[:60]}: {m:.3f} ms [{min(t):.3f}, {max(t):.3f}]  "
+                      f"x{m / med[0]:.4f} vs first  {'same nodes/found/calls' if same else 'MISMATCH'}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--libs", required=True, action="append")
@@ -79,7 +111,8 @@ def main():
     ap.add_argument("--share-index", action="store_true",
                     help="one index for every arm (same library; knobs read per call only)")
     ap.add_argument("--rank-ce", default="", help="query counts: time rank_ce (loss + grad_q) per arm instead")
-    ap.add_argument("--reps", type=int, default=9, help="--rank-ce: repetitions")
+    ap.add_argument("--categorize", default="", help="query counts: time categorize per arm instead")
+    ap.add_argument("--reps", type=int, default=9, help="--rank-ce / --categorize: repetitions")
     ap.add_argument("--clusters", type=int, default=0, help="0: flat tree; G: root -> G random clusters -> leaves")
     args = ap.parse_args()
     pkg = cobweb_pkg.load()
@@ -108,7 +141,7 @@ def main():
         with env(knobs[p]):
             L._lib = L.load_library(os.path.abspath(p.split("@")[0]), strict=False)
             ix = pkg.index.CobwebIndex(fs["mean"], fs["var"], fs["parent"], fs["node_of_sentence"], device=dev)
-            if not args.rank_ce:
+            if not args.rank_ce and not args.categorize:
                 ix.set_filter(1)
                 ix.score_topk(Q, args.k)
         arms.append(ix)
@@ -116,6 +149,9 @@ def main():
     torch.cuda.empty_cache()
     if args.rank_ce:
         rank_ce_ab(paths, arms, Q, [int(v) for v in args.rank_ce.split(",")], args.reps)
+        return
+    if args.categorize:
+        categorize_ab(paths, arms, Q, [int(v) for v in args.categorize.split(",")], args.reps, args.k)
         return
     call = {p: [] for p in paths}
     fg = {p: [] for p in paths}
