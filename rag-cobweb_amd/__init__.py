@@ -2,7 +2,7 @@
 
 Package layout (directory ``rag-cobweb_amd/``, imported as ``rag_cobweb_amd`` via
 ``cobweb_pkg.load()``):
-  csrc/      HIP kernels for gfx950 + the C-ABI runtime -> libcwq.so
+  csrc/      HIP kernels for gfx950 + the C-ABI runtime (the host files behind cwq_handle.h) -> libcwq.so
   _lib.py    ctypes binding of include/cobweb_query.h
   index.py   CobwebIndex: the device-resident flattened tree + query calls
   tree.py    host concept tree, reference JSON format, BFS flattening

@@ -8,33 +8,16 @@
 //     then anisotropic rows:                            A = 1/sigma, B = mu/sigma   [DP][ld_an]
 //   dim-major ("transposed") so a wave's 64 lanes = 64 consecutive rows read one
 //   coalesced 256-B line per dimension.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-#include <chrono>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "../../include/cobweb_query.h"
-#include "cwq_internal.h"
-
-using namespace cwq;
+#include "cwq_handle.h"
 
 static thread_local std::string g_err;
 
-static int fail(int code, const std::string& msg) {
+namespace cwq {
+int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+}  // namespace cwq
 
 // Run-time knobs (environment variables, read where they are used: tests switch them in-process)
 static int env_int(const char* name, int dflt) {   // the value of a non-empty setting, else dflt
@@ -47,324 +30,6 @@ static bool env_off(const char* name) {   // a non-empty setting that parses to 
 }
 static bool env_set(const char* name) { return getenv(name) != nullptr; }
 
-#define HIPCHK(expr)                                                                                \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) return fail(CWQ_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-namespace {
-
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(dev);
-  }
-  ~DevGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-// Bump allocator over the handle's workspace.
-struct Bump {
-  char* base;
-  size_t off = 0, cap;
-  Bump(void* b, size_t c) : base((char*)b), cap(c) {}
-  template <class T>
-  T* take(size_t n) {
-    off = (off + 255) & ~size_t(255);
-    T* p = (T*)(base + off);
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
-// A grow-on-demand buffer of the handle: kept between calls, freed and allocated anew (rounded up
-// to `round` bytes) when a call needs more than it holds.  busy: an event to wait for before the
-// free -- earlier calls' kernels may still read a device buffer (cwq_index::busy).
-struct GrowBuf {
-  enum Kind { kDevice, kPinned, kMapped };   // hipMalloc / pinned host / mapped coherent host memory
-  Kind kind;
-  size_t round;
-  const char* what;   // the error message; one that ends in '(' gets the size appended
-  void* p = nullptr;
-  size_t size = 0;
-  template <class T>
-  T* as() const {
-    return (T*)p;
-  }
-  void release() {
-    if (p) (void)(kind == kDevice ? hipFree(p) : hipHostFree(p));
-    p = nullptr;
-    size = 0;
-  }
-  int reserve(size_t b, hipEvent_t busy = nullptr) {
-    if (b <= size) return CWQ_OK;
-    if (busy) (void)hipEventSynchronize(busy);
-    release();
-    b = (size_t)round_up((int64_t)b, (int64_t)round);
-    const hipError_t e = kind == kDevice   ? hipMalloc(&p, b)
-                         : kind == kPinned ? hipHostMalloc(&p, b, hipHostMallocDefault)
-                                           : hipHostMalloc(&p, b, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) {
-      std::string msg = what;
-      if (msg.back() == '(') msg += std::to_string(b) + " B)";
-      return fail(CWQ_ERR_OOM, msg);
-    }
-    size = b;
-    return CWQ_OK;
-  }
-};
-
-}  // namespace
-
-struct cwq_index {
-  int device = 0;
-  int64_t n_nodes = 0, n_sent = 0;
-  int D = 0, DP = 0;
-  int NI = 0, NL = 0, NL_iso = 0, NL_an = 0;
-  int64_t ld_int = 0, ld_iso = 0, ld_an = 0;
-  int max_depth = 0;
-  int cus = 256;
-  std::vector<std::pair<int, int>> levels;   // internal-node ranges, one per depth
-  int* d_lv = nullptr;                       // device copy: level starts + end [levels + 1]
-  int* sel_ctr = nullptr;                    // per-call path: fused select counter (probe with fused prep)
-  float root_w0 = 0.f, root_logdet0 = 0.f;   // the root's w and logdet (host copies)
-  std::vector<void*> allocs;
-  size_t bytes = 0;
-  // row data
-  float *int_A = nullptr, *int_B = nullptr, *iso_M = nullptr, *an_A = nullptr, *an_B = nullptr;
-  RowMeta* row_meta = nullptr;
-  int *row_par = nullptr, *row_flags = nullptr, *row_bfs = nullptr;
-  int *row_depth = nullptr, *int_depth = nullptr;   // depth of each leaf-class row / internal node (call-time level weights)
-  float* logdet_row = nullptr;
-  float *logdet_int = nullptr, *w_int = nullptr;
-  int *par_int = nullptr, *int_child_begin = nullptr, *int_child_end = nullptr, *int_nchild = nullptr;
-  int *int_bfs = nullptr, *int_has_sent = nullptr;
-  bool any_int_sent = false;   // an internal node holds sentences (categorize: heap replay only)
-  int *int_leaf_a0 = nullptr, *int_leaf_a1 = nullptr, *int_leaf_b0 = nullptr, *int_leaf_b1 = nullptr;
-  int64_t *sent_ptr = nullptr, *sent_ids = nullptr;
-  int* row_of_sent = nullptr;
-  int* node_src = nullptr;
-  float* dummy = nullptr;
-  // bf16-MFMA filter operands for the isotropic rows (cwq_mfma.hip): row-major
-  // fp32 (exact rerank, DP wide) and bf16 hi-part (GEMM, DPB wide) copies padded to
-  // whole 256-row tiles, per-row / per-tile bound constants, the threshold sample
-  int64_t ld_f = 0;
-  int DPB = 0;
-  float *iso_Mf = nullptr, *iso_c = nullptr;   // iso_c: centre [D] (root mean)
-  uint16_t* iso_Mb = nullptr;
-  RowF* iso_rf = nullptr;
-  TileF* iso_tf = nullptr;
-  // int8 operands of the stream filter pass (launch_rows_i8), built on the first small-batch
-  // call: 0 not yet, 1 built, -1 off (CWQ_STREAM_I8=0, DPB % 64, or too little free memory)
-  int8_t* iso_Mq = nullptr;
-  RowF* iso_rf8 = nullptr;
-  TileF* iso_tf8 = nullptr;   // iso_tf with the int8 tile maxima (the batch filter's int8 launches)
-  int i8_state = 0;
-  bool i8_by_size = false;   // the panel was built with the index by the size rule (ensure_i8), not by a knob
-  // the batch filter's early int8 schedule (fg_i8_from) went back to the quarter rule: a call
-  // on it passed too many candidates or re-ran a query (until cwq_set_filter)
-  bool i8_early_off = false;
-  bool i8_early_ran = false;   // the current call ran the early schedule
-  std::vector<int> tile_uni_prefix;   // prefix counts of uniform row tiles (all_uniform per launch range)
-  int n_multi_tiles = 0;              // tiles with several parents (TileF uniform 2)
-  // the same tables for the categorize key min(BF[parent], lp) (cwq_categorize through the
-  // filter): lp with the 2*pi constant, no prefix term (invL 0), the categorize usable rule
-  RowF* cat_rf = nullptr;
-  TileF* cat_tf = nullptr;
-  std::vector<int> cat_uni_prefix;
-  float cat_dconst = 0.f;
-  int n_samp = 0, ld_s = 0;                    // sample rows, padded to 256
-  int n_hub = 0;                               // of n_samp: the hub rows (largest row terms R0)
-  // group-centred filter rows (cwq_group.hip; clustered trees): the isotropic rows below a
-  // depth-1 internal node g are centred at its mean grp_c[g]; grp_par[p] = the group of
-  // internal node p's rows (-1: root-centred), grp_F[p] = hs / invL of p's rows (Fast),
-  // grp_Fc[p] = their categorize hs.  grp_mode: the filters read the shifted prefix tables.
-  bool grp_mode = false;
-  int G = 0;
-  int64_t n_grp_rows = 0;
-  // the cut plan_groups chose (host copies, build_prune reads them): the group of every
-  // internal node (-1: a top node -- the root and the ancestors of the group centres, which
-  // every query computes exactly), each group's centre (internal id) and whether its rows are
-  // centred there (grp_ok; a group that fails the centring rule is still a pruning group)
-  std::vector<int> cut_gint, cut_centre;
-  std::vector<char> cut_ok;
-  int cut_maxdep = 0, cut_top = 0;   // deepest centre, number of top nodes (filter_info)
-  float* grp_c = nullptr;
-  int* grp_par = nullptr;
-  double *grp_F = nullptr, *grp_Fc = nullptr;
-  // group pruning of the Fast query (cwq_prune.hip; group-centred trees with every level
-  // weight >= 0): the pruning group of each internal node, group-major internal node lists,
-  // per-group bound constants.  prune_ctr: the last call's stage-B pair count (diagnostics).
-  bool prune_ok = false;
-  int *prn_gint = nullptr, *gi_ptr = nullptr, *gi_nodes = nullptr;
-  // top nodes in BFS order (root first) with their parents' list positions and depths; per
-  // group the list position of its centre's parent (a top node)
-  int *top_nodes = nullptr, *top_ppos = nullptr, *top_dep = nullptr, *grp_tpos = nullptr;
-  int n_top = 0, top_maxdep = 0;
-  // auto mode's record of the filter on this index: queries filtered / re-run exactly; when
-  // at least 9 in 10 of >= 256 queries had to be re-run (the bounds too loose for this
-  // tree's rows), auto mode takes the exact scan from then on (same results, less work)
-  int64_t filt_q = 0, filt_fb = 0;
-  bool filt_auto_off = false;
-  int filt_off_calls = 0;   // auto-mode Fast calls on the exact scan since the filter went off
-  // categorize: the last call's queries all went to the two-level replay, so the next call
-  // launches the second list with the first replay (gated on its status) instead of after
-  // reading that status back (categorize_impl)
-  bool cat_two_spec = false;
-  bool cat_tail_done = false;   // categorize_impl: the node tails are cleared, nothing runs after its last sync
-  // categorize, calls of <= 64 queries: the list paths, or straight to the exact lazy replay
-  // (simulate_lazy_runs_kernel; categorize_impl's path choice).  The choice is measured: per-query
-  // wall time of each path (EMA), the faster one taken, the other tried every kCatExplore calls
-  // -- but the lazy path is only ever tried while the list paths recently left queries to the
-  // DENSE re-run (cat_dense_seen: ties nested deeper than the two-level replay certifies; a
-  // tree the lists resolve, C2's or a flat one, never pays for the trial).  lazy_stats: the last
-  // call's queries replayed lazily straight away / after the list paths (cwq_last_lazy_stats)
-  // [0]: calls of <= 64 queries, [1]: batches (tried on any tree whose widest node fits the
-  // replay's arena, max_fanout <= kLzFanout: the lazy replays of a batch run side by side)
-  double cat_ema_list[2] = {-1.0, -1.0}, cat_ema_direct[2] = {-1.0, -1.0};
-  int cat_dense_seen = 0, cat_pol_calls[2] = {0, 0};
-  bool cat_pref_direct[2] = {false, false};
-  int max_fanout = 0;   // the most children (internal + leaf rows) of one internal node
-  int64_t lazy_stats[2] = {0, 0};
-  // categorize: calls since the counting pass last resolved a query (after 8 such calls
-  // cat_count_kernel is skipped -- every query then goes to the replay anyway -- and tried
-  // again every kCatCountRetry calls)
-  int cat_count_idle = 0;
-  int prn_gmax = 1;   // the most internal nodes of one pruning group
-  int prn_maxdep = 0, prn_mindep = 1;   // deepest / shallowest internal node of any group
-  int *gi_dep = nullptr, *gi_ppos = nullptr;   // per group-list entry: depth, the parent's list position
-  int* blk_grp = nullptr;   // per 16-row block of isotropic rows: the pruning group of all its rows (-1: mixed)
-  int *gs_ptr = nullptr, *gs_rows = nullptr;   // per group: up to 64 usable isotropic rows (the seed threshold)
-  GroupBound* gbound = nullptr;
-  int* prune_ctr = nullptr;     // device [8]: per chunk pair count + claim counters, [4] the call's pair total
-  int64_t prune_nq = 0;         // queries the last Fast call pruned (0: none)
-  // internal-node bounds (hierarchical trees): bf16 operand rows, their RowF constants,
-  // row-major fp32 A/B copies for the exact chain in final_kernel.  int_path (default):
-  // the Fast filter reads the path prefix P of leaf parents only, so there is one row per
-  // leaf parent (and the root), its b' vectors summed along the path (cwq_mfma.hip
-  // int_path_prep) -- one GEMM, no prefix passes.  Otherwise (CWQ_INT_PATH=0 at index
-  // creation) one row per internal node, levels 0-1 together and each deeper level from
-  // a new 256-row tile, then prefix_bounds_kernel level by level.
-  bool int_bounds = false;
-  bool int_path = true;
-  int DPB2 = 0;
-  int64_t ld_i2 = 0;                  // operand rows (padded to 256)
-  uint16_t* int_Mb2 = nullptr;
-  RowF* int_rf2 = nullptr;
-  int* int_rowid = nullptr;           // operand row -> internal id (-1: padding)
-  RowF* int_nrf = nullptr;            // int_path: int_rf2 by internal id (par -2: no operand row), PathB
-  float *int_Ar = nullptr, *int_Br = nullptr;
-  float root_w = 1.f, root_ld = 0.f;   // the root's level weight and logdet (host copies)
-  int* samp_rows = nullptr;
-  uint16_t* iso_Sb = nullptr;
-  int64_t stats[6] = {0, 0, 0, 0, 0, 0};   // cwq_last_stats
-  // timing (cwq_set_timing)
-  bool timing = false;
-  int filter = -1;   // cwq_set_filter
-  int n_fg_launch = 0;   // filter launches of the last chunk (timing report)
-  int n_fg_i8 = 0;       // of the call's filter launches (all chunks), those on the int8 operands
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  float t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // workspace.  Every query call carves its buffers from `ws`; the call's kernels may
-  // still be running when it returns, so the end of each call records `ws_ev` on its
-  // stream and the next call makes its own stream wait for it (ws_begin / ws_end):
-  // calls on different streams reuse the workspace in order.
-  std::mutex mu;
-  GrowBuf ws{GrowBuf::kDevice, 1 << 20, "workspace hipMalloc failed ("};
-  size_t ws_budget = 0;   // query-chunk workspace budget, from the free memory at the first call
-  hipEvent_t ws_ev = nullptr;
-  bool ws_ev_live = false;
-  bool ws_idle = false;   // set by a call that ends with its stream synchronized: no event needed
-  // the per-query filter flags on the host (int): coherent (fine-grained) memory --
-  // final_wide_kernel writes the flags of the per-call path straight into it; the batch paths
-  // copy into it (one D2H per chunk)
-  GrowBuf hflags{GrowBuf::kMapped, 1, "hipHostMalloc failed"};
-  // cwq_score_topk_host: pinned staging of the host queries, their device copy, and mapped
-  // (coherent) host memory the kernels write the results into
-  GrowBuf hq{GrowBuf::kPinned, 1 << 16, "host query staging allocation failed"};
-  GrowBuf dq{GrowBuf::kDevice, 1 << 16, "host query staging allocation failed"};
-  GrowBuf hout{GrowBuf::kMapped, 1 << 16, "host result buffer allocation failed"};
-  // fallback re-runs (cwq_score_topk / cwq_categorize): gathered queries, their results
-  // and the device index lists, kept between calls
-  GrowBuf fb{GrowBuf::kDevice, 1 << 20, "fallback hipMalloc failed ("};
-  GrowBuf fb2{GrowBuf::kDevice, 1, "categorize fallback buffers"};   // categorize's filter fallback (its exact re-run uses fb itself)
-
-  template <class T>
-  int alloc(T** p, size_t n) {
-    void* q = nullptr;
-    const size_t b = std::max<size_t>(n, 1) * sizeof(T);
-    if (hipMalloc(&q, b) != hipSuccess) return fail(CWQ_ERR_OOM, "hipMalloc failed (" + std::to_string(b) + " B)");
-    allocs.push_back(q);
-    bytes += b;
-    *p = (T*)q;
-    return CWQ_OK;
-  }
-  template <class T>
-  int upload(T** p, const std::vector<T>& v, hipStream_t s) {
-    int rc = alloc(p, v.size());
-    if (rc) return rc;
-    if (!v.empty()) HIPCHK(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    return CWQ_OK;
-  }
-  // earlier calls' kernels may still read the device buffers: the event to wait for before a free
-  hipEvent_t busy() const { return ws_ev_live ? ws_ev : nullptr; }
-  int reserve(size_t b) { return ws.reserve(b, busy()); }
-  // start of a query call on stream s: wait for the previous call's use of the workspace
-  int ws_begin(hipStream_t s) {
-    if (!ws_ev && hipEventCreateWithFlags(&ws_ev, hipEventDisableTiming) != hipSuccess)
-      return fail(CWQ_ERR_HIP, "hipEventCreate failed");
-    // always wait, also on the previous call's stream handle: a destroyed stream's handle
-    // can come back as a new stream.  The per-call path ends synchronized (ws_idle), so
-    // it leaves no live event and queues no barrier packet here.
-    if (ws_ev_live && hipStreamWaitEvent(s, ws_ev, 0) != hipSuccess)
-      return fail(CWQ_ERR_HIP, "hipStreamWaitEvent failed");
-    return CWQ_OK;
-  }
-  // end of a query call: the workspace is busy until the work queued on s so far is done
-  int ws_end(hipStream_t s) {
-    if (!ws_ev) return fail(CWQ_ERR_HIP, "workspace event missing");
-    if (ws_idle) {   // every kernel of the call has finished: the workspace is free now
-      ws_idle = false;
-      ws_ev_live = false;
-      return CWQ_OK;
-    }
-    if (hipEventRecord(ws_ev, s) != hipSuccess) {
-      // the event no longer marks this call's work: wait for it here instead
-      ws_ev_live = false;
-      (void)hipStreamSynchronize(s);
-      return fail(CWQ_ERR_HIP, "hipEventRecord failed");
-    }
-    ws_ev_live = true;
-    return CWQ_OK;
-  }
-  ~cwq_index() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (ws_ev_live) (void)hipEventSynchronize(ws_ev);
-    if (ws_ev) (void)hipEventDestroy(ws_ev);
-    for (void* p : allocs) (void)hipFree(p);
-    for (GrowBuf* b : {&ws, &fb, &fb2, &hflags, &hq, &dq, &hout}) b->release();
-  }
-};
-
-// RAII: a query entry point's use of the handle workspace on stream s (cwq_index::ws_begin)
-struct WsUse {
-  cwq_index* ix;
-  hipStream_t s;
-  int rc;
-  WsUse(cwq_index* i, hipStream_t st) : ix(i), s(st) {
-    rc = ix->ws_begin(s);
-  }
-  ~WsUse() {
-    if (rc == CWQ_OK) (void)ix->ws_end(s);   // ws_begin failed: nothing was queued on s
-  }
-};
-
 #ifndef CWQ_BUILD_ID
 #define CWQ_BUILD_ID "unversioned"
 #endif
@@ -375,7 +40,6 @@ extern "C" const char* cwq_build_id(void) { return kBuildId + 13; }
 extern "C" const char* cwq_last_error(void) { return g_err.c_str(); }
 
 namespace {
-
 // Error-bound constants of the filter (cwq_mfma.hip header): fp32 accumulation of the
 // MFMA products (2x the textbook (n-1)u, n = DPB + 64), norm/centring rounding, and the
 // relative slack that covers the fp32 evaluation of both the bounds and the exact keys.
@@ -1001,9 +665,6 @@ int build_prune(cwq_index* ix, const float* mean, const VarSrc& var, const std::
   return CWQ_OK;
 }
 
-}  // namespace
-
-namespace {
 // cwq_index_create / cwq_index_create_cv: `var` is either the full [n_nodes][D] array or
 // the compact per-node form (VarSrc); both give the same index.
 bool use_int_bounds(const cwq_index* ix);
@@ -1347,6 +1008,7 @@ extern "C" int cwq_index_create_cv(int device, int64_t n_nodes, int32_t dim, con
 // cwq_index_create_from_fit (cwq_fitindex.hip): mean and the compact variances (VarSrc with
 // its an_map) already on the device; parent / node_of_sentence on the host.  Errors go to
 // cwq_last_error (msg_out: the message, for the caller's own error slot).
+
 namespace cwq {
 int index_create_device(int device, int64_t n_nodes, int32_t dim, const float* mean, const VarSrc& var,
                         const int64_t* parent, const int64_t* node_of_sentence, int64_t n_sent,
@@ -1356,7 +1018,7 @@ int index_create_device(int device, int64_t n_nodes, int32_t dim, const float* m
     DevGuard dg(device);
     rc = index_create_impl(device, n_nodes, dim, mean, var, parent, node_of_sentence, n_sent, level_w, n_w, s, out);
   }
-  if (msg_out) *msg_out = g_err.c_str();
+  if (msg_out) *msg_out = cwq_last_error();
   return rc;
 }
 int index_fail(int code, const char* msg) { return fail(code, msg); }
@@ -1410,83 +1072,10 @@ extern "C" int cwq_index_cut_info(const cwq_index* idx, int64_t* o) {
   return CWQ_OK;
 }
 
-// Scan configuration of one query call (cwq_kernels.hip scan_cfg_begin): fixed from the
-// call's total query count, so every chunk and workspace estimate of the call agrees.
-struct ScanCfgScope {
-  explicit ScanCfgScope(int64_t nq) { scan_cfg_begin(nq); }
-  ~ScanCfgScope() { scan_cfg_end(); }
-};
-
 namespace {
-
-// A query entry point's hold on the handle, in this order: its lock, its device, its use of the
-// workspace on stream s (rc: ws_begin's result) and the call's scan configuration.
-struct QueryCall {
-  std::lock_guard<std::mutex> lk;
-  DevGuard dg;
-  WsUse wu;
-  ScanCfgScope scs;
-  int rc;
-  QueryCall(cwq_index* ix, int64_t nq, hipStream_t s) : lk(ix->mu), dg(ix->device), wu(ix, s), scs(nq), rc(wu.rc) {}
-};
-
-// Gather some queries of a call, run a sub-call on them, scatter its results back: idx holds the
-// queries' indices in the call (pageable host memory, so close() synchronises the stream: idx
-// must outlive its upload to d_idx).
-struct SubCall {
-  hipStream_t s;
-  int64_t n;
-  int64_t* d_idx;
-  int open(const std::vector<int64_t>& idx, int64_t* d, hipStream_t st) {
-    s = st;
-    n = (int64_t)idx.size();
-    d_idx = d;
-    HIPCHK(hipMemcpyAsync(d_idx, idx.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-    return CWQ_OK;
-  }
-  int gather(const float* q, int64_t D, float* qsub) {   // qsub[i] = q[idx[i]]
-    HIPCHK(launch_copy_rows(q, D, d_idx, qsub, D, nullptr, n, D, s));
-    return CWQ_OK;
-  }
-  int scatter(const void* src, int64_t words, void* dst) {   // dst[idx[i]] = src[i], rows of 4-byte words
-    HIPCHK(launch_copy_rows(src, words, nullptr, dst, words, d_idx, n, words, s));
-    return CWQ_OK;
-  }
-  int close() {
-    HIPCHK(hipStreamSynchronize(s));
-    return CWQ_OK;
-  }
-};
-
-}  // namespace
-
 // ---------------------------------------------------------------------------
 // Query orchestration
 // ---------------------------------------------------------------------------
-namespace {
-
-constexpr int kQPad = 128;   // queries are padded to a multiple of the largest query block
-
-struct Chunk {
-  int nq = 0;           // valid queries
-  int64_t nq_pad = 0;
-  float* X = nullptr;   // [nq_pad][DP]
-  float *S_int = nullptr, *P = nullptr, *BF = nullptr, *LPF = nullptr;   // [nq_pad][NI]
-  // P / S_int layout (pidx): query-major [q][ldP] (the exact pass); node-major [node][nq_pad]
-  // after the path-sum bounds (run_internal_bounds)
-  int64_t ldP = 1;
-  int pT = 0;
-  const float4* qi2 = nullptr;   // path-sum bounds: the queries' [x'^2, x'] norms (PathB)
-  // group-centred rows (grp_mode): the filters' prefix tables [nq_pad][NI] -- Fast
-  // [Pg_lo, Pg_hi] and categorize [Pc_lo, Pc_hi] -- and the per-(query, group) shifts
-  float *Pg_lo = nullptr, *Pg_hi = nullptr, *Pc_lo = nullptr, *Pc_hi = nullptr;
-  double* gsh = nullptr;
-  float* Tseed = nullptr;   // group pruning's seed threshold [nq] (a lower bound of tau_K), or none
-  int grp_done = -1;   // the group tables run_internal's fused pass wrote: -1 none, 0 Fast, 1 + categorize
-  // call-time level weights (cwq_lweight.hip): the exact passes read these instead of the index's
-  const float* w_int = nullptr;    // [NI]
-  const RowMeta* meta = nullptr;   // [NL]
-};
 
 // The group-centred rows' prefix tables of a chunk (after the exact internal pass wrote
 // c.P): q = the chunk's [nq][D] queries.  No-op without grp_mode.
@@ -1597,13 +1186,17 @@ int prune_internal(cwq_index* ix, Chunk& c, const float* q, int K, Bump& b, hipS
   ix->prune_nq += nq;
   return CWQ_OK;
 }
+}  // namespace
 
+namespace cwq {
 // The path-sum dots of a chunk after run_internal_bounds (int_path), or none.
 PathB path_b(const cwq_index* ix, const Chunk& c) {
   if (c.pT && ix->int_path && c.qi2 && ix->int_nrf) return PathB{c.P, c.ldP, c.qi2, ix->int_nrf};
   return PathB{nullptr, 0, nullptr, nullptr};
 }
+}  // namespace cwq
 
+namespace {
 // Query blocks of a launch; a multiple of 8 under the XCD-aware mapping (the
 // extra blocks exit at once).
 int n_qblocks_for(int64_t nq, int kl) {
@@ -1703,9 +1296,11 @@ int internal_prefixes(cwq_index* ix, Chunk& c, hipStream_t s, float* BF, float* 
   if (grp) c.grp_done = grp_cat;
   return CWQ_OK;
 }
+}  // namespace
 
-int run_internal(cwq_index* ix, Chunk& c, hipStream_t s, bool bf_lpf = true, const float* q = nullptr,
-                 int grp_cat = -1) {
+namespace cwq {
+int run_internal(cwq_index* ix, Chunk& c, hipStream_t s, bool bf_lpf, const float* q,
+                 int grp_cat) {
   float* BF = bf_lpf ? c.BF : nullptr;
   float* LPF = bf_lpf ? c.LPF : nullptr;
   if (ix->NI == 0) return CWQ_OK;
@@ -1733,7 +1328,9 @@ int run_internal(cwq_index* ix, Chunk& c, hipStream_t s, bool bf_lpf = true, con
     HIPCHK(launch_scan(false, EPI_RAW, false, kl, c.X, ix->int_A, ix->int_B, a, nslab2, s));
   return internal_prefixes(ix, c, s, BF, LPF, dfull, q, grp_cat);
 }
+}  // namespace cwq
 
+namespace {
 int fg_order();
 void fg_groups(int n_qt, int& qg, int& rg);
 
@@ -1745,7 +1342,9 @@ bool use_int_bounds(const cwq_index* ix) {
   if (!ix->int_bounds || ix->NL_an > 0 || ix->grp_mode) return false;
   return !env_off("CWQ_INT_BOUND");
 }
+}  // namespace
 
+namespace cwq {
 size_t int_bounds_bytes(const cwq_index* ix, int64_t nqf) {
   return ix->int_bounds ? (size_t)nqf * ix->DPB2 * 2 + (size_t)nqf * 16 + (size_t)nqf * 4 + 5 * 256 : 0;
 }
@@ -1828,7 +1427,9 @@ int run_internal_bounds(cwq_index* ix, Chunk& c, const float* q, int64_t nqf, Bu
                                   ix->levels[lv].second, ix->par_int, ix->w_int, ix->logdet_int, Sroot, s));
   return CWQ_OK;
 }
+}  // namespace cwq
 
+namespace {
 IntChain int_chain(const cwq_index* ix) { return IntChain{ix->int_Ar, ix->int_Br, ix->par_int, ix->w_int, ix->logdet_int}; }
 
 // Fast top-K over a small isotropic segment with many queries: the lane-per-query scan
@@ -1850,13 +1451,15 @@ bool use_small_scan(const cwq_index* ix, int64_t nq, int K) {
   const int64_t small_waves = (nq + kWave - 1) / kWave * small_scan_slabs(nq, ix->NL_iso);
   return small_waves * 10 >= rs_waves * 9 || (small_waves * 2 >= rs_waves && small_waves >= 4 * (int64_t)ix->cus);
 }
+}  // namespace
 
+namespace cwq {
 // One scan over both leaf-row segments.
 // seg_mask: bit 0 = isotropic segment, bit 1 = anisotropic; TOPK lists start at
 // slab_off0 (slots before it are filled by the caller).
 int run_leaf_scan(cwq_index* ix, const Chunk& c, int epi, bool cat, int kl, float dconst, float* out, int64_t ldo,
                   float* pkey, float* paux, int* prow, int K, int* nslab_total_out, hipStream_t s,
-                  int seg_mask = 3, int slab_off0 = 0, int max_lists = INT_MAX) {
+                  int seg_mask, int slab_off0, int max_lists) {
   if (c.pT && ((seg_mask & 1) ? ix->NL : ix->NL_an) > 0)   // the scans read query-major exact prefixes
     return fail(CWQ_ERR_ARG, "leaf scan after node-major prefix bounds (internal error)");
   const int tq = scan_tq(kl);
@@ -1930,19 +1533,24 @@ int run_leaf_scan(cwq_index* ix, const Chunk& c, int epi, bool cat, int kl, floa
   }
   return CWQ_OK;
 }
+}  // namespace cwq
 
+namespace {
 // Workspace for one chunk: X + internal arrays.
 // Workspace of one chunk: X + the [nq][NI] internal arrays -- S_int and P always; BF and
 // LPF (path bottleneck, full log_prob) only for categorize / log_prob (`full`).
 size_t group_bytes_per_query(const cwq_index* ix) {
   return ix->grp_mode ? (size_t)ix->G * 16 + (size_t)4 * std::max(ix->NI, 1) * 4 + 5 * 256 + prune_bytes_per_query(ix) : 0;
 }
-size_t chunk_bytes(const cwq_index* ix, int64_t nq_pad, bool full = true) {
+}  // namespace
+
+namespace cwq {
+size_t chunk_bytes(const cwq_index* ix, int64_t nq_pad, bool full) {
   return (size_t)nq_pad * ix->DP * 4 + (full ? 4 : 2) * (size_t)nq_pad * std::max(ix->NI, 1) * 4 + 8 * 256 +
          (size_t)nq_pad * group_bytes_per_query(ix);
 }
 
-void carve_chunk(cwq_index* ix, Bump& b, Chunk& c, int nq, bool full = true) {
+void carve_chunk(cwq_index* ix, Bump& b, Chunk& c, int nq, bool full) {
   c.nq = nq;
   c.nq_pad = round_up(nq, kQPad);
   c.X = b.take<float>((size_t)c.nq_pad * ix->DP);
@@ -1969,7 +1577,7 @@ void carve_chunk(cwq_index* ix, Bump& b, Chunk& c, int nq, bool full = true) {
 // Query-chunk size that keeps the per-chunk workspace within the budget (16 GiB by
 // default -- 288 GB of HBM hold it beside the largest indexes; CWQ_WS_BUDGET_MB; at
 // least 128 queries).
-int64_t chunk_queries(const cwq_index* ix, int64_t nq, size_t per_query_extra, bool full = true) {
+int64_t chunk_queries(const cwq_index* ix, int64_t nq, size_t per_query_extra, bool full) {
   const size_t per_q = (size_t)ix->DP * 4 + (full ? 4 : 2) * (size_t)std::max(ix->NI, 1) * 4 + per_query_extra +
                        group_bytes_per_query(ix);
   // budget: CWQ_WS_BUDGET_MB, else 40% of what the device has free (plus the workspace
@@ -1993,14 +1601,14 @@ int64_t chunk_queries(const cwq_index* ix, int64_t nq, size_t per_query_extra, b
   c = std::max<int64_t>(kQPad, c / kQPad * kQPad);
   return std::min(nq, c);
 }
-}  // namespace
-
-namespace {
 
 constexpr int kFiltMinRows = 16384;   // automatic mode: below this the exact scan is as fast
 constexpr int kFiltMaxK = 64;         // the filter serves the list-based top-k path (k <= 64)
 constexpr int kFgRecPerQ = 512;       // candidate-record slots per query (append buffer)
 constexpr int kFgDirPerQ = 256;       // direct-record slots per query (tiles past kFgCap)
+}  // namespace cwq
+
+namespace {
 // Clustered (group-centred) trees: a query's whole cluster can pass -- categorize keys tie at
 // the cluster node's lp for every row of the cluster (~1,000 rows at C2) -- so the record
 // buffers hold 4x as many per query (48 KB instead of 12 KB per query).
@@ -2881,7 +2489,6 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
   }
   return CWQ_OK;
 }
-
 }  // namespace
 
 // The paired entry points (device / host memory) open alike: the argument checks; then, under the
@@ -2992,451 +2599,6 @@ extern "C" int cwq_set_timing(cwq_index* ix, int enable) {
 extern "C" int cwq_last_timing(cwq_index* ix, float* out) {
   if (!ix || !out) return fail(CWQ_ERR_ARG, "NULL argument");
   for (int i = 0; i < 8; ++i) out[i] = ix->t_ms[i];
-  return CWQ_OK;
-}
-
-namespace {
-
-// Call-time level weights (cwq_lweight.hip): the chunk's RowMeta' / w_int' in the workspace,
-// read by the exact passes and the backward's coefficient kernels instead of the index's.
-size_t lw_operand_bytes(const cwq_index* ix, const float* level_w) {
-  return level_w ? (size_t)std::max(ix->NL, 1) * sizeof(RowMeta) + (size_t)std::max(ix->NI, 1) * 4 + 2 * 256 : 0;
-}
-int lw_operands(const cwq_index* ix, Bump& b, const float* level_w, int n_w, const RowMeta** meta, const float** w_int,
-                hipStream_t s) {
-  *meta = ix->row_meta;
-  *w_int = ix->w_int;
-  if (!level_w) return CWQ_OK;
-  RowMeta* m = b.take<RowMeta>(std::max(ix->NL, 1));
-  float* w = b.take<float>(std::max(ix->NI, 1));
-  HIPCHK(launch_lw_operands(level_w, n_w, ix->row_meta, ix->row_depth, ix->NL, ix->int_depth, ix->NI, m, w, s));
-  *meta = m;
-  *w_int = w;
-  return CWQ_OK;
-}
-int lw_check(const float* level_w, int32_t n_w) {
-  (void)level_w;
-  if (n_w < 0 || n_w > kLwMaxLevels) return fail(CWQ_ERR_ARG, "n_w must be in [0, 64]");
-  return CWQ_OK;
-}
-
-int rank_scores_impl(cwq_index* ix, const float* q, int64_t nq, const float* level_w, int n_w, float* out,
-                     void* stream);
-
-}  // namespace
-
-extern "C" int cwq_rank_scores(cwq_index* ix, const float* q, int64_t nq, float* out, void* stream) {
-  if (!ix || (!q && nq > 0) || (!out && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
-  return rank_scores_impl(ix, q, nq, nullptr, 0, out, stream);
-}
-
-extern "C" int cwq_rank_scores_w(cwq_index* ix, const float* q, int64_t nq, const float* level_w, int32_t n_w,
-                                 float* out, void* stream) {
-  if (!ix || !q || !out) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
-  if (int rc = lw_check(level_w, n_w)) return rc;
-  return rank_scores_impl(ix, q, nq, level_w, n_w, out, stream);
-}
-
-namespace {
-
-int rank_scores_impl(cwq_index* ix, const float* q, int64_t nq, const float* level_w, int n_w, float* out,
-                     void* stream) {
-  if (nq == 0) return CWQ_OK;
-  hipStream_t s = (hipStream_t)stream;
-  QueryCall call(ix, nq, s);
-  if (call.rc) return call.rc;
-  const int64_t cq = chunk_queries(ix, nq, (size_t)ix->NL * 4, false);
-  int rc;
-  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
-    const int nqc = (int)std::min(cq, nq - q0);
-    const int64_t nq_pad = round_up(nqc, kQPad);
-    if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(ix->NL, 1) * 4 + 8 * 256 +
-                          lw_operand_bytes(ix, level_w))))
-      return rc;
-    Bump b(ix->ws.p, ix->ws.size);
-    Chunk c;
-    carve_chunk(ix, b, c, nqc, false);
-    float* rowkey = b.take<float>((size_t)nq_pad * std::max(ix->NL, 1));
-    if ((rc = lw_operands(ix, b, level_w, n_w, &c.meta, &c.w_int, s))) return rc;
-    HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
-    if ((rc = run_internal(ix, c, s, false))) return rc;
-    if ((rc = run_leaf_scan(ix, c, EPI_KEY, false, 16, 0.f, rowkey, ix->NL, nullptr, nullptr, nullptr, 1, nullptr, s)))
-      return rc;
-    HIPCHK(launch_gather_sentences(rowkey, ix->NL, nqc, ix->row_of_sent, ix->n_sent, out + q0 * ix->n_sent, s));
-  }
-  return CWQ_OK;
-}
-
-
-// The backward's launch plan: slabs, leaf-sum pieces, threads per node and workspace bytes per
-// query -- functions of the index alone (a query's gradient is the same in any batch).
-struct GradPlan {
-  int rps, ns_iso, ns_an, ns_int, nslab, nsplit, P;
-  std::vector<int> lv;
-  size_t per_q;
-};
-
-GradPlan grad_plan(const cwq_index* ix) {
-  GradPlan g;
-  const int NL = ix->NL, NI = ix->NI;
-  g.rps = grad_rows_per_slab((int64_t)ix->NL_iso + 2 * ((int64_t)ix->NL_an + NI), ix->cus);
-  g.ns_iso = (ix->NL_iso + g.rps - 1) / g.rps;
-  g.ns_an = (ix->NL_an + g.rps - 1) / g.rps;
-  g.ns_int = (NI + g.rps - 1) / g.rps;
-  g.nslab = g.ns_iso + g.ns_an + g.ns_int;
-  g.nsplit = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)ix->max_fanout + 4095) / 4096));
-  g.P = ix->max_fanout > 64 ? 16 : 1;
-  for (auto& l : ix->levels) {
-    g.lv.push_back(l.first);
-    g.lv.push_back(l.second);
-  }
-  g.per_q = ((size_t)2 * std::max(NL, 1) + (size_t)(2 + g.nsplit) * std::max(NI, 1) + (size_t)g.nslab * ix->DP) * 4;
-  return g;
-}
-
-// The coefficient arrays and the partial tiles of one chunk (nq16 * per_q bytes + 8 * 256).
-float* grad_carve(const cwq_index* ix, const GradPlan& gp, Bump& b, int nqc, int qtiles, GradCoefArgs& ca) {
-  const int NL = ix->NL, NI = ix->NI;
-  const size_t nq16 = (size_t)qtiles * kXQ;
-  memset(&ca, 0, sizeof(ca));
-  ca.n_sent = ix->n_sent;
-  ca.nq = nqc;
-  ca.qtiles = qtiles;
-  ca.NL = NL;
-  ca.NL_iso = ix->NL_iso;
-  ca.NI = NI;
-  ca.sent_ptr = ix->sent_ptr;
-  ca.sent_ids = ix->sent_ids;
-  ca.meta = ix->row_meta;
-  ca.leaf_a0 = ix->int_leaf_a0;
-  ca.leaf_a1 = ix->int_leaf_a1;
-  ca.leaf_b0 = ix->int_leaf_b0;
-  ca.leaf_b1 = ix->int_leaf_b1;
-  ca.child_begin = ix->int_child_begin;
-  ca.child_end = ix->int_child_end;
-  ca.w_int = ix->w_int;
-  ca.lv = gp.lv.data();
-  ca.nlev = (int)ix->levels.size();
-  ca.P = gp.P;
-  ca.nsplit = gp.nsplit;
-  ca.coefL = b.take<float>(nq16 * std::max(NL, 1));
-  ca.hL = b.take<float>(nq16 * std::max(NL, 1));
-  ca.cz = b.take<float>(nq16 * std::max(NI, 1) * gp.nsplit);
-  ca.cI = b.take<float>(nq16 * std::max(NI, 1));
-  ca.coefI = b.take<float>(nq16 * std::max(NI, 1));
-  return b.take<float>(nq16 * (size_t)gp.nslab * ix->DP);
-}
-
-// The streaming reduction over the three row classes and the slab sum, from the coefficients.
-int grad_streams(const cwq_index* ix, const GradPlan& gp, const GradCoefArgs& ca, float* part, const float* q, int nqc,
-                 int qtiles, float* grad_q, hipStream_t s) {
-  const int NL = ix->NL, NI = ix->NI, DP = ix->DP;
-  GradStreamArgs g;
-  memset(&g, 0, sizeof(g));
-  g.q = q;
-  g.nq = nqc;
-  g.qtiles = qtiles;
-  g.D = ix->D;
-  g.DP = DP;
-  g.rows_per_slab = gp.rps;
-  g.part = part;
-  if (ix->NL_iso > 0) {   // isotropic rows: row-major fp32 means, 1/v folded into the coefficient
-    g.M = ix->iso_Mf;
-    g.nrows = ix->NL_iso;
-    g.coef = ca.coefL;
-    g.ncoef = NL;
-    g.coef_base = 0;
-    g.slab_off = 0;
-    HIPCHK(launch_grad_stream(g, s));
-  }
-  g.M = nullptr;
-  if (ix->NL_an > 0) {
-    g.A = ix->an_A;
-    g.B = ix->an_B;
-    g.ld = ix->ld_an;
-    g.nrows = ix->NL_an;
-    g.coef = ca.coefL;
-    g.ncoef = NL;
-    g.coef_base = ix->NL_iso;
-    g.slab_off = gp.ns_iso;
-    HIPCHK(launch_grad_stream(g, s));
-  }
-  if (NI > 0) {
-    g.A = ix->int_A;
-    g.B = ix->int_B;
-    g.ld = ix->ld_int;
-    g.nrows = NI;
-    g.coef = ca.coefI;
-    g.ncoef = NI;
-    g.coef_base = 0;
-    g.slab_off = gp.ns_iso + gp.ns_an;
-    HIPCHK(launch_grad_stream(g, s));
-  }
-  HIPCHK(launch_grad_reduce(part, gp.nslab, qtiles, nqc, DP, ix->D, grad_q, s));
-  return CWQ_OK;
-}
-
-
-// The weight gradient of one chunk (cwq_lweight.hip) from the coefficient pass's hL / cI and
-// the raw sums the exact passes left: the chunk's S_int and sraw (EPI_RAW over the leaf rows).
-size_t lw_grad_bytes_per_q(const cwq_index* ix) {   // sraw is counted by the caller (nq_pad lines)
-  return (size_t)lw_parts(ix->NL, ix->NI) * (ix->max_depth + 1) * 8;
-}
-int lw_grad(const cwq_index* ix, const Chunk& c, const GradCoefArgs& ca, const float* sraw, bool is_lp, double* part,
-            int n_w, float* grad_w, hipStream_t s) {
-  LwGradArgs g;
-  memset(&g, 0, sizeof(g));
-  g.nq = ca.nq;
-  g.qtiles = ca.qtiles;
-  g.NL = ix->NL;
-  g.NI = ix->NI;
-  g.nlev = ix->max_depth + 1;
-  g.n_w = n_w;
-  g.hL = ca.hL;
-  g.cI = ca.cI;
-  g.S_row = sraw;
-  g.ldS_row = std::max(ix->NL, 1);
-  g.S_int = c.S_int;
-  g.ldS_int = std::max(ix->NI, 1);
-  g.logdet_row = is_lp ? nullptr : ix->logdet_row;
-  g.logdet_int = ix->logdet_int;
-  g.row_depth = ix->row_depth;
-  g.int_depth = ix->int_depth;
-  g.part = part;
-  g.grad_w = grad_w;
-  HIPCHK(launch_lw_grad(g, s));
-  return CWQ_OK;
-}
-
-// Backward of cwq_rank_scores (cwq_grad.hip): the coefficient pass, the streaming reduction
-// over the three row classes, the slab sum.  Needs q, grad_out and the index only; the weight
-// gradient also needs the forward's raw sums, which it recomputes (internal pass + EPI_RAW).
-int rank_scores_backward_impl(cwq_index* ix, const float* q, int64_t nq, const float* grad_out, const float* level_w,
-                              int n_w, float* grad_q, float* grad_w, void* stream) {
-  if (nq == 0) return CWQ_OK;
-  hipStream_t s = (hipStream_t)stream;
-  QueryCall call(ix, nq, s);
-  if (call.rc) return call.rc;
-  if (grad_w && ix->max_depth + 1 > kLwMaxLevels) return fail(CWQ_ERR_ARG, "weight gradient: tree deeper than 64 levels");
-  const GradPlan gp = grad_plan(ix);
-  const int NL = ix->NL;
-  const size_t lw_q = grad_w ? (size_t)std::max(NL, 1) * 4 + lw_grad_bytes_per_q(ix) : 0;
-  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, gp.per_q + lw_q, false), 4096);
-  int rc;
-  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
-    const int nqc = (int)std::min(cq, nq - q0);
-    const int64_t nq_pad = round_up(nqc, kQPad);
-    const int qtiles = (nqc + kXQ - 1) / kXQ;
-    const size_t nq16 = (size_t)qtiles * kXQ;
-    if ((rc = ix->reserve(nq16 * gp.per_q + 8 * 256 + lw_operand_bytes(ix, level_w) +
-                          (grad_w ? chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(NL, 1) * 4 +
-                                        nq16 * lw_grad_bytes_per_q(ix) + 8 * 256
-                                  : 0))))
-      return rc;
-    Bump b(ix->ws.p, ix->ws.size);
-    GradCoefArgs ca;
-    float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
-    if ((rc = lw_operands(ix, b, level_w, n_w, &ca.meta, &ca.w_int, s))) return rc;
-    ca.G = grad_out + q0 * ix->n_sent;
-    HIPCHK(launch_grad_coef(ca, s));
-    if (grad_q && (rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
-    if (!grad_w) continue;
-    Chunk c;
-    carve_chunk(ix, b, c, nqc, false);
-    float* sraw = b.take<float>((size_t)nq_pad * std::max(NL, 1));
-    double* lwp = b.take<double>(nq16 * lw_grad_bytes_per_q(ix) / 8);
-    HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
-    if ((rc = run_internal(ix, c, s, false))) return rc;
-    if ((rc = run_leaf_scan(ix, c, EPI_RAW, false, 16, 0.f, sraw, NL, nullptr, nullptr, nullptr, 1, nullptr, s)))
-      return rc;
-    if ((rc = lw_grad(ix, c, ca, sraw, false, lwp, n_w, grad_w + q0 * n_w, s))) return rc;
-  }
-  return CWQ_OK;
-}
-
-// Cross-entropy ranking loss over all sentence scores with its gradient, the target's score
-// and rank (cwq_loss.hip): the exact scan's row keys stay in the workspace,
-// the softmax goes straight into the backward's coefficient layout.
-int rank_ce_impl(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
-                 const float* level_w, int n_w, float* loss, float* grad_q, float* grad_w, float* target_score,
-                 int64_t* rank, void* stream) {
-  if (nq == 0) return CWQ_OK;
-  hipStream_t s = (hipStream_t)stream;
-  QueryCall call(ix, nq, s);
-  if (call.rc) return call.rc;
-  if (grad_w && ix->max_depth + 1 > kLwMaxLevels) return fail(CWQ_ERR_ARG, "weight gradient: tree deeper than 64 levels");
-  const int NL = ix->NL;
-  const int npart = (NL + kCePart - 1) / kCePart;
-  const GradPlan gp = grad_plan(ix);
-  const bool grad = grad_q || grad_w;
-  // per query: its row keys, the partials and (m, 1/z, row); the backward's arrays when wanted;
-  // the rows' raw sums and the fp64 partial lines of the weight gradient
-  const size_t ce_q = (size_t)std::max(npart, 1) * 12 + 12;
-  const size_t lw_q = grad_w ? (size_t)std::max(NL, 1) * 4 + lw_grad_bytes_per_q(ix) : 0;
-  const size_t per_q = (size_t)std::max(NL, 1) * 4 + ce_q + (grad ? gp.per_q : 0) + lw_q;
-  const int64_t cq = std::min<int64_t>(chunk_queries(ix, nq, per_q, false), 4096);
-  int rc;
-  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
-    const int nqc = (int)std::min(cq, nq - q0);
-    const int64_t nq_pad = round_up(nqc, kQPad);
-    const int qtiles = (nqc + kXQ - 1) / kXQ;
-    const size_t nq16 = (size_t)qtiles * kXQ;
-    if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + (size_t)nq_pad * std::max(NL, 1) * 4 + nq16 * ce_q +
-                          (grad ? nq16 * gp.per_q : 0) + 24 * 256 + lw_operand_bytes(ix, level_w) +
-                          (grad_w ? (size_t)nq_pad * std::max(NL, 1) * 4 + nq16 * lw_grad_bytes_per_q(ix) + 4 * 256
-                                  : 0))))
-      return rc;
-    Bump b(ix->ws.p, ix->ws.size);
-    Chunk c;
-    carve_chunk(ix, b, c, nqc, false);
-    float* rowkey = b.take<float>((size_t)nq_pad * std::max(NL, 1));
-    CeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rowkey = rowkey;
-    a.ldr = NL;
-    a.NL = NL;
-    a.nq = nqc;
-    a.qtiles = qtiles;
-    a.npart = npart;
-    a.invT = 1.f / temperature;
-    a.sent_ptr = ix->sent_ptr;
-    a.sent_ids = ix->sent_ids;
-    a.row_bfs = ix->row_bfs;
-    a.row_of_sent = ix->row_of_sent;
-    a.n_sent = ix->n_sent;
-    a.target = target + q0;
-    a.pm = b.take<float>(nq16 * std::max(npart, 1));
-    a.pz = b.take<float>(nq16 * std::max(npart, 1));
-    a.pc = b.take<int>(nq16 * std::max(npart, 1));
-    a.mz = b.take<float2>(nq16);
-    a.rtq = b.take<int>(nq16);
-    a.loss = loss + q0;
-    a.tscore = target_score ? target_score + q0 : nullptr;
-    a.rank = rank ? rank + q0 : nullptr;
-    if ((rc = lw_operands(ix, b, level_w, n_w, &c.meta, &c.w_int, s))) return rc;
-    // the weight gradient reads every row's lp': the scan writes it beside the key (EPI_KEYLP)
-    float* rowlp = grad_w ? b.take<float>((size_t)nq_pad * std::max(NL, 1)) : nullptr;
-    HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
-    if ((rc = run_internal(ix, c, s, false))) return rc;
-    if ((rc = run_leaf_scan(ix, c, grad_w ? EPI_KEYLP : EPI_KEY, false, 16, 0.f, rowkey, NL, rowlp, nullptr, nullptr, 1,
-                            nullptr, s)))
-      return rc;
-    HIPCHK(launch_ce_reduce(a, s));
-    if (!grad) continue;
-    GradCoefArgs ca;
-    float* part = grad_carve(ix, gp, b, nqc, qtiles, ca);
-    ca.meta = c.meta;
-    ca.w_int = c.w_int;
-    HIPCHK(launch_ce_coef(a, ca.meta, ix->NL_iso, ca.coefL, ca.hL, s));
-    HIPCHK(launch_grad_tree(ca, s));
-    if (grad_q && (rc = grad_streams(ix, gp, ca, part, q + q0 * ix->D, nqc, qtiles, grad_q + q0 * ix->D, s))) return rc;
-    if (!grad_w) continue;
-    double* lwp = b.take<double>(nq16 * lw_grad_bytes_per_q(ix) / 8);
-    if ((rc = lw_grad(ix, c, ca, rowlp, true, lwp, n_w, grad_w + q0 * n_w, s))) return rc;
-  }
-  return CWQ_OK;
-}
-
-}  // namespace
-
-extern "C" int cwq_rank_scores_backward(cwq_index* ix, const float* q, int64_t nq, const float* grad_out,
-                                        float* grad_q, void* stream) {
-  if (!ix || !q || !grad_out || !grad_q) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
-  return rank_scores_backward_impl(ix, q, nq, grad_out, nullptr, 0, grad_q, nullptr, stream);
-}
-
-extern "C" int cwq_rank_scores_backward_w(cwq_index* ix, const float* q, int64_t nq, const float* grad_out,
-                                          const float* level_w, int32_t n_w, float* grad_q, float* grad_w,
-                                          void* stream) {
-  if (!ix || !q || !grad_out || (!grad_q && !grad_w)) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
-  if (int rc = lw_check(level_w, n_w)) return rc;
-  return rank_scores_backward_impl(ix, q, nq, grad_out, level_w, n_w, grad_q, n_w > 0 ? grad_w : nullptr, stream);
-}
-
-extern "C" int cwq_rank_ce(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
-                           float* loss, float* grad_q, float* target_score, int64_t* rank, void* stream) {
-  if (!ix || !q || !target || !loss) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
-  if (!std::isfinite(temperature) || !(temperature > 0.f))
-    return fail(CWQ_ERR_ARG, "temperature must be finite and > 0");
-  return rank_ce_impl(ix, q, nq, target, temperature, nullptr, 0, loss, grad_q, nullptr, target_score, rank, stream);
-}
-
-extern "C" int cwq_rank_ce_w(cwq_index* ix, const float* q, int64_t nq, const int64_t* target, float temperature,
-                             const float* level_w, int32_t n_w, float* loss, float* grad_q, float* grad_w,
-                             float* target_score, int64_t* rank, void* stream) {
-  if (!ix || !q || !target || !loss) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq < 0) return fail(CWQ_ERR_ARG, "nq < 0");
-  if (int rc = lw_check(level_w, n_w)) return rc;
-  if (!std::isfinite(temperature) || !(temperature > 0.f))
-    return fail(CWQ_ERR_ARG, "temperature must be finite and > 0");
-  return rank_ce_impl(ix, q, nq, target, temperature, level_w, n_w, loss, grad_q, n_w > 0 ? grad_w : nullptr,
-                      target_score, rank, stream);
-}
-
-extern "C" int cwq_node_logprob(cwq_index* ix, const float* q, int64_t nq, int32_t full, float* out, void* stream) {
-  if (!ix || (!q && nq > 0) || (!out && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq == 0) return CWQ_OK;
-  hipStream_t s = (hipStream_t)stream;
-  QueryCall call(ix, nq, s);
-  if (call.rc) return call.rc;
-  const float dconst = full ? (float)((double)ix->D * (double)logf(2.0f * (float)M_PI)) : 0.f;
-  const int64_t cq = chunk_queries(ix, nq, (size_t)ix->NL * 4);
-  int rc;
-  for (int64_t q0 = 0; q0 < nq; q0 += cq) {
-    const int nqc = (int)std::min(cq, nq - q0);
-    const int64_t nq_pad = round_up(nqc, kQPad);
-    if ((rc = ix->reserve(chunk_bytes(ix, nq_pad) + (size_t)nq_pad * std::max(ix->NL, 1) * 4 + 8 * 256))) return rc;
-    Bump b(ix->ws.p, ix->ws.size);
-    Chunk c;
-    carve_chunk(ix, b, c, nqc);
-    float* sleaf = b.take<float>((size_t)nq_pad * std::max(ix->NL, 1));
-    HIPCHK(launch_pad_queries(q + q0 * ix->D, nqc, ix->D, c.X, c.nq_pad, ix->DP, s));
-    if ((rc = run_internal(ix, c, s))) return rc;
-    if ((rc = run_leaf_scan(ix, c, EPI_RAW, false, 16, 0.f, sleaf, ix->NL, nullptr, nullptr, nullptr, 1, nullptr, s)))
-      return rc;
-    HIPCHK(launch_node_lp(c.S_int ? c.S_int : ix->dummy, std::max(ix->NI, 1), sleaf, std::max(ix->NL, 1), nqc,
-                          ix->node_src, ix->logdet_int, ix->logdet_row, dconst, ix->n_nodes, out + q0 * ix->n_nodes, s));
-  }
-  return CWQ_OK;
-}
-
-extern "C" int cwq_prefix_bounds(cwq_index* ix, const float* q, int64_t nq, float* lo, float* hi, float* exact,
-                                 void* stream) {
-  if (!ix || !q || !lo || !hi || !exact) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (nq <= 0 || nq > 4096) return fail(CWQ_ERR_ARG, "nq must be in [1, 4096]");
-  if (!ix->int_bounds)
-    return fail(CWQ_ERR_ARG, "no internal-node bounds on this index (flat tree, no isotropic leaf rows or too deep)");
-  hipStream_t s = (hipStream_t)stream;
-  QueryCall call(ix, nq, s);
-  if (call.rc) return call.rc;
-  const int64_t nq_pad = round_up(nq, kQPad), nqf = round_up(nq, kFgTile);
-  int rc;
-  if ((rc = ix->reserve(chunk_bytes(ix, nq_pad, false) + int_bounds_bytes(ix, nqf) + 64 * 256))) return rc;
-  Bump b(ix->ws.p, ix->ws.size);
-  Chunk c;
-  carve_chunk(ix, b, c, (int)nq, false);
-  const size_t n = (size_t)nq * ix->NI * 4;
-  HIPCHK(launch_pad_queries(q, nq, ix->D, c.X, c.nq_pad, ix->DP, s));
-  if ((rc = run_internal(ix, c, s, false))) return rc;
-  HIPCHK(hipMemcpyAsync(exact, c.P, n, hipMemcpyDeviceToDevice, s));
-  const size_t nall = (size_t)c.nq_pad * ix->NI * 4;
-  HIPCHK(hipMemsetAsync(c.P, 0xff, nall, s));   // NaN where the bound pass writes nothing
-  HIPCHK(hipMemsetAsync(c.S_int, 0xff, nall, s));
-  if ((rc = run_internal_bounds(ix, c, q, nqf, b, s))) return rc;
-  const PathB pb = path_b(ix, c);
-  if (pb.dot) {   // path-sum dots, node-major [NI][nq_pad] -> bounds [nq][NI]
-    HIPCHK(launch_pathb_expand(pb, (int)nq, ix->NI, lo, hi, s));
-  } else if (c.pT) {   // node-major [NI][nq_pad] -> [nq][NI]
-    HIPCHK(launch_transpose(c.P, ix->NI, nq, c.ldP, lo, ix->NI, s));
-    HIPCHK(launch_transpose(c.S_int, ix->NI, nq, c.ldP, hi, ix->NI, s));
-  } else {
-    HIPCHK(hipMemcpyAsync(lo, c.P, n, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(hi, c.S_int, n, hipMemcpyDeviceToDevice, s));
-  }
   return CWQ_OK;
 }
 
@@ -4263,76 +3425,5 @@ extern "C" int cwq_categorize_host(cwq_index* ix, const float* q, int64_t nq, in
   memcpy(nodes, hn, (size_t)nq * k * 8);
   memcpy(n_found, hf, fb);
   if (n_calls) memcpy(n_calls, hc, (size_t)nq * 8);
-  return CWQ_OK;
-}
-
-extern "C" int cwq_welford_groups(const float* X, int64_t n_rows, int32_t dim, const int64_t* order,
-                                  const int64_t* group_ptr, int64_t n_groups, float* count, float* mean,
-                                  float* meanSq, void* stream) {
-  if (!X || !order || !group_ptr || !count || !mean || !meanSq || dim <= 0 || n_rows < 0)
-    return fail(CWQ_ERR_ARG, "bad arguments");
-  if (n_groups > 65535) return fail(CWQ_ERR_ARG, "at most 65535 groups per call");
-  HIPCHK(launch_welford_groups(X, dim, order, group_ptr, n_groups, count, mean, meanSq, (hipStream_t)stream));
-  return CWQ_OK;
-}
-
-// PCA + ICA whitening transform (F4) -- PCAICAWhiteningModel.transform, src/whitening/pca_ica.py:30-51.
-extern "C" int cwq_whiten(const float* X, int64_t n, int32_t d_in, const float* mean, const float* comps,
-                          int32_t d_pca, const float* denom, const float* unmix, int32_t d_out, float* out,
-                          float* work, void* stream) {
-  if (n < 0 || d_in <= 0 || d_pca <= 0 || (unmix && d_out <= 0)) return fail(CWQ_ERR_ARG, "bad whitening shape");
-  if (n == 0) return CWQ_OK;
-  if (!X || !mean || !comps || !denom || !out || (unmix && !work)) return fail(CWQ_ERR_ARG, "NULL argument");
-  hipStream_t s = (hipStream_t)stream;
-  float* pca = unmix ? work : out;
-  HIPCHK(launch_gemm_nt_f32(X, n, d_in, mean, comps, d_pca, denom, pca, s));
-  if (unmix) HIPCHK(launch_gemm_nt_f32(pca, n, d_pca, nullptr, unmix, d_out, nullptr, out, s));
-  return CWQ_OK;
-}
-
-// ---- whitening fit: column sums, TN Gram, FastICA's G pass (cwq_whitenfit.hip) ----
-static bool wf_dim_ok(int32_t d) { return d >= 1 && d <= 1024; }
-
-extern "C" int cwq_whitenfit_slab(void) { return kWfSlab; }
-
-extern "C" int64_t cwq_col_sums_work_bytes(int64_t n, int32_t d) {
-  if (n < 0 || !wf_dim_ok(d)) return -1;
-  return ((n + kWfSlab - 1) / kWfSlab) * d * (int64_t)sizeof(double);
-}
-
-extern "C" int64_t cwq_gram_acc_work_bytes(int64_t n, int32_t da, int32_t db) {
-  if (n < 0 || !wf_dim_ok(da) || !wf_dim_ok(db)) return -1;
-  return ((n + kWfSlab - 1) / kWfSlab) * da * db * (int64_t)sizeof(float);
-}
-
-extern "C" int64_t cwq_ica_g_work_bytes(int64_t n, int32_t p) {
-  if (n < 0 || !wf_dim_ok(p)) return -1;
-  return ((n + 127) / 128) * p * (int64_t)sizeof(double);
-}
-
-extern "C" int cwq_col_sums(const float* X, int64_t n, int32_t d, double* acc, void* work, void* stream) {
-  if (n < 0 || !wf_dim_ok(d)) return fail(CWQ_ERR_ARG, "bad column-sum shape (n >= 0, d in [1, 1024])");
-  if (!X || !acc || !work) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (n == 0) return CWQ_OK;
-  HIPCHK(launch_col_sums(X, n, d, acc, (double*)work, (hipStream_t)stream));
-  return CWQ_OK;
-}
-
-extern "C" int cwq_gram_acc(const float* A, const float* B, int64_t n, int32_t da, int32_t db, const float* ctr_a,
-                            const float* ctr_b, double* acc, void* work, void* stream) {
-  if (n < 0 || !wf_dim_ok(da) || !wf_dim_ok(db))
-    return fail(CWQ_ERR_ARG, "bad Gram shape (n >= 0, da and db in [1, 1024])");
-  if (!A || !B || !acc || !work) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (n == 0) return CWQ_OK;
-  HIPCHK(launch_gram_acc(A, B, n, da, db, ctr_a, ctr_b, acc, (float*)work, (hipStream_t)stream));
-  return CWQ_OK;
-}
-
-extern "C" int cwq_ica_g(const float* X1, int64_t n, int32_t p, const float* W, float* G, double* gsum, void* work,
-                         void* stream) {
-  if (n < 0 || !wf_dim_ok(p)) return fail(CWQ_ERR_ARG, "bad ICA shape (n >= 0, p in [1, 1024])");
-  if (!X1 || !W || !G || !gsum || !work) return fail(CWQ_ERR_ARG, "NULL argument");
-  if (n == 0) return CWQ_OK;
-  HIPCHK(launch_ica_g(X1, n, p, W, G, gsum, (double*)work, (hipStream_t)stream));
   return CWQ_OK;
 }

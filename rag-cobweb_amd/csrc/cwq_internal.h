@@ -1,5 +1,5 @@
 // Internal declarations shared by the libcwq kernels (cwq_kernels.hip) and the
-// C-ABI host runtime (cwq_api.hip).  Not part of the public interface.
+// C-ABI host runtime (cwq_api.hip and the host files behind cwq_handle.h).  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -245,7 +245,7 @@ struct PruneArgs {
   const int* top_nodes; const int* top_ppos; const int* top_dep; int n_top, top_maxdep;
   const int* grp_tpos;
   const GroupBound* gb;
-  double* kpart;                // [2][nq][G]: P0-free part of KUB, and the margin's magnitude term
+  double* kpart;                // [3][nq][G]: P0-free part of KUB, the margin's magnitude term, the centre estimate kp0
   float* S; float* P;           // [nq][ldS]
   float* Plo; float* Phi;       // the filters' shifted prefix tables (group-centred rows)
   const int* grp; const double* F; double* sh;   // centring group, F, shifts + errors [2][nq][G]

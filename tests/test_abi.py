@@ -28,6 +28,14 @@ def test_library_exports_every_header_symbol(pkg):
     assert L.cwq_version() >= 100
 
 
+def test_build_sources_are_the_hip_files_present(pkg):
+    """The library links with unresolved symbols allowed, so a .hip file left out of
+    build.SOURCES would show only when a function it defines is first called."""
+    csrc = os.path.join(ROOT, "rag-cobweb_amd", "csrc")
+    assert len(pkg.build.SOURCES) == len(set(pkg.build.SOURCES))
+    assert set(pkg.build.SOURCES) == {f for f in os.listdir(csrc) if f.endswith(".hip")}
+
+
 def test_error_path_without_gpu_compute(pkg):
     """Argument validation happens before any device work."""
     L = pkg.lib()
