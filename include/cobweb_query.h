@@ -323,6 +323,60 @@ int cwq_categorize_host(cwq_index* idx, const float* q, int64_t nq, int32_t k, i
 int cwq_last_stats(cwq_index* idx, int64_t* out6);
 
 /*
+ * Masked Fast top-k: cwq_score_topk restricted to an allowed sentence set (no reference
+ * counterpart: the reference always ranks every sentence).  One mask per call,
+ * shared by the call's queries.
+ *
+ * The result for a query is its full cwq_score_topk ranking (key descending, then lower node
+ * index, then lower sentence id) with the sentences that are not allowed removed, cut to k:
+ * ids and scores are that ranking's bit for bit.  When fewer than k allowed sentences are in
+ * the tree the tail is -1 / -inf, as for k > n_sent.  A sentence that is not in the tree
+ * (node_of_sentence -1) is never returned, whatever its bit.  Any k >= 1 is accepted.
+ *
+ * cwq_mask_create
+ *   bits    device uint32 words, ceil(n_sent / 32) of them: bit (s % 32) of word (s / 32),
+ *           least significant bit first, set = sentence s is allowed.  Copied: the caller
+ *           may free it when the call returns (the call synchronises `stream`, as
+ *           cwq_index_create does).
+ *   n_sent  must equal the index's (CWQ_ERR_ARG otherwise)
+ * A mask remembers the index it was built for by that index's serial number, not by its
+ * address: cwq_score_topk_masked with another index -- also a new index at the old address
+ * -- is CWQ_ERR_ARG with a message.  A mask holds no pointer into its index, so it may
+ * outlive it, and the two may be destroyed in either order.  A mask is immutable after its
+ * creation and may be shared by calls on different streams and threads.
+ * cwq_mask_info(out4): [allowed sentences that are in the tree, live isotropic rows, live
+ * anisotropic rows (a row is live when one of its sentences is allowed), device bytes].
+ *
+ * cwq_score_topk_masked: arguments as cwq_score_topk.  It takes one of three paths, with
+ * identical results:
+ *   1 over-fetch  cwq_score_topk's own work at some k' <= 64 into buffers of the handle, the
+ *                 allowed entries kept in order; a query with fewer than min(k, allowed)
+ *                 survivors is redone by path 2 (every allowed sentence outside the unmasked
+ *                 top-k' ranks below all of it, so the survivors are a prefix of the answer)
+ *   2 gathered    an exact fp32 scan of the live rows only, through the mask's row lists
+ *   3 sort        k > 64: every row's exact key, the rows that are not live set to -inf, the
+ *                 full sort of cwq_score_topk's k > 64 path, a masked expansion
+ * For k <= 64 the choice follows the allowed fraction f: over-fetch when k' = ceil(2 k / f)
+ * is at most 64 (calls of <= 64 queries) or 40 (larger calls, whose unmasked filter gets
+ * expensive past that), else gathered.  Env CWQ_MASK_PATH, read per call: 0 / unset
+ * automatic, 1 over-fetch first (k' = 64 below the rule's fraction), 2 gathered only.  The
+ * choice never changes a result.  The call synchronises
+ * `stream` on path 1 (it reads the per-query flags back).  A mask without a live row
+ * returns all -1 / -inf without a scan.  CWQ_ERR_ARG before any device work for a NULL idx /
+ * mask / q / ids or k <= 0; nq == 0 is a no-op.
+ * cwq_last_mask_stats(out4): [path (1, 2, 3), k' (path 1, else 0), queries redone by the
+ * gathered scan (path 1), live rows of the mask].  After path 1, cwq_last_stats describes
+ * the unmasked call at k'.
+ */
+typedef struct cwq_mask cwq_mask;
+int cwq_mask_create(cwq_index* idx, const uint32_t* bits, int64_t n_sent, void* stream, cwq_mask** out);
+int cwq_mask_destroy(cwq_mask* m);
+int cwq_mask_info(const cwq_mask* m, int64_t* out4);
+int cwq_score_topk_masked(cwq_index* idx, const cwq_mask* m, const float* q, int64_t nq, int32_t k, int64_t* ids,
+                          float* scores, void* stream);
+int cwq_last_mask_stats(const cwq_index* idx, int64_t* out4);
+
+/*
  * Group pruning of the Fast query (clustered trees whose rows are
  * group-centred, every level weight >= 0): per (query, depth-1 group) a certified upper
  * bound of every key in the group; the exact internal pass runs for each query's best group

@@ -49,6 +49,11 @@ SIGNATURES = {
     "cwq_set_filter": (_c.c_int, [_P, _c.c_int]),
     "cwq_last_stats": (_c.c_int, [_P, _P]),
     "cwq_last_prune_stats": (_c.c_int, [_P, _P]),
+    "cwq_mask_create": (_c.c_int, [_P, _P, _I64, _P, _c.POINTER(_P)]),
+    "cwq_mask_destroy": (_c.c_int, [_P]),
+    "cwq_mask_info": (_c.c_int, [_P, _P]),
+    "cwq_score_topk_masked": (_c.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P]),
+    "cwq_last_mask_stats": (_c.c_int, [_P, _P]),
     "cwq_score_topk_host": (_c.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "cwq_categorize_host": (_c.c_int, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P]),
     "cwq_whiten": (_c.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _I32, _P, _P, _P]),

@@ -2513,6 +2513,18 @@ static int stage_host(cwq_index* ix, const float* q, size_t qbytes, size_t obyte
   return CWQ_OK;
 }
 
+namespace cwq {
+// for cwq_score_topk_masked (cwq_maskcalls.hip), which holds the handle itself: the last call's
+// record cleared, and cwq_score_topk's work
+void topk_begin(cwq_index* ix) { topk_reset(ix); }
+int score_topk_unmasked(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,
+                        hipStream_t s) {
+  const int rc = score_topk_impl(ix, q, nq, k, ids, scores, s, true);
+  if (!rc) note_filter(ix);
+  return rc;
+}
+}  // namespace cwq
+
 extern "C" int cwq_score_topk(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,
                               void* stream) {
   if (int rc = topk_args(ix, q, nq, k, ids)) return rc;

@@ -1,6 +1,6 @@
 // The query library's host layer behind the C ABI: the handle (struct cwq_index), the per-call
 // scopes, the query chunk, and the declarations of the host functions that cross a file.
-// Host only: included by cwq_api.hip, cwq_rank.hip and cwq_fitcalls.hip and by nothing else; the
+// Host only: included by cwq_api.hip, cwq_rank.hip, cwq_fitcalls.hip and cwq_maskcalls.hip and by nothing else; the
 // kernel sources share cwq_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -100,9 +100,14 @@ struct GrowBuf {
   }
 };
 
+// A number no other index of this process has had: what a cwq_mask remembers of its index (an
+// index pointer can come back for a new index once the old one is destroyed).
+uint64_t next_index_serial();   // cwq_maskcalls.hip
+
 }  // namespace cwq
 
 struct cwq_index {
+  uint64_t serial = cwq::next_index_serial();
   int device = 0;
   int64_t n_nodes = 0, n_sent = 0;
   int D = 0, DP = 0;
@@ -274,6 +279,10 @@ struct cwq_index {
   // and the device index lists, kept between calls
   GrowBuf fb{GrowBuf::kDevice, 1 << 20, "fallback hipMalloc failed ("};
   GrowBuf fb2{GrowBuf::kDevice, 1, "categorize fallback buffers"};   // categorize's filter fallback (its exact re-run uses fb itself)
+  // cwq_score_topk_masked, over-fetch path: the unmasked top-k' ids / scores and the per-query
+  // short flags (not from `ws`: score_topk_impl carves that anew per chunk)
+  GrowBuf mk{GrowBuf::kDevice, 1 << 16, "masked top-k buffers hipMalloc failed ("};
+  int64_t mask_stats[4] = {0, 0, 0, 0};   // cwq_last_mask_stats
 
   template <class T>
   int alloc(T** p, size_t n) {
@@ -329,7 +338,29 @@ struct cwq_index {
     if (ws_ev_live) (void)hipEventSynchronize(ws_ev);
     if (ws_ev) (void)hipEventDestroy(ws_ev);
     for (void* p : allocs) (void)hipFree(p);
-    for (GrowBuf* b : {&ws, &fb, &fb2, &hflags, &hq, &dq, &hout}) b->release();
+    for (GrowBuf* b : {&ws, &fb, &fb2, &mk, &hflags, &hq, &dq, &hout}) b->release();
+  }
+};
+
+// An allowed-sentence set for cwq_score_topk_masked (cwq_maskcalls.hip builds it): immutable after
+// cwq_mask_create, so calls on any stream may share it; it holds no pointer into its index.
+struct cwq_mask {
+  uint64_t serial = 0;   // of the index it was built for
+  int device = 0;
+  int64_t n_sent = 0;
+  int NL_iso = 0, NL_an = 0;
+  void* mem = nullptr;   // one allocation: the arrays below
+  size_t bytes = 0;
+  uint32_t* bits = nullptr;   // the caller's bitset (private copy)
+  uint8_t* live = nullptr;    // [NL] the row holds an allowed sentence
+  int *rows_iso = nullptr, *rows_an = nullptr;   // live rows of each segment (segment row ids), ascending
+  int n_iso = 0, n_an = 0;
+  int64_t n_allowed = 0;   // allowed sentences that are in the tree
+  ~cwq_mask() {
+    if (mem) {
+      DevGuard dg(device);
+      (void)hipFree(mem);
+    }
   }
 };
 
@@ -431,5 +462,9 @@ int run_leaf_scan(cwq_index* ix, const Chunk& c, int epi, bool cat, int kl, floa
 size_t chunk_bytes(const cwq_index* ix, int64_t nq_pad, bool full = true);
 void carve_chunk(cwq_index* ix, Bump& b, Chunk& c, int nq, bool full = true);
 int64_t chunk_queries(const cwq_index* ix, int64_t nq, size_t per_query_extra, bool full = true);
+// (the unmasked Fast call for a caller that holds the handle: topk_reset, score_topk_impl + note_filter)
+void topk_begin(cwq_index* ix);
+int score_topk_unmasked(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,
+                        hipStream_t s);
 
 }  // namespace cwq

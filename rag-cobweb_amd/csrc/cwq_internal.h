@@ -1030,6 +1030,53 @@ struct FitDev {
 };
 int fit_fail(int code, const char* msg);   // sets cwq_fit_last_error's message; returns code
 
+// ---- masked Fast top-k (cwq_mask.hip; cwq_score_topk_masked) ----
+// Arguments of the gathered exact scan over one segment's live rows (mask_scan_kernel).
+struct MaskScanArgs {
+  int DP;               // padded dimension
+  int nq;               // valid queries
+  int n_live;           // entries of `list`
+  int rows_per_slab;    // list entries per slab (a multiple of mask_scan_tile)
+  int n_qblocks;        // blocks of 64 queries (shared-query form: of 16)
+  int seg_base;         // global leaf-row id of segment row 0
+  const int* list;      // [n_live] segment rows, ascending
+  int64_t ld;           // anisotropic rows: leading dimension of the dim-major A / B
+  const RowMeta* meta;  // of the segment
+  const int* par;       // of the segment
+  const float* P;       // [nq_pad][ldP] exact prefixes (query-major)
+  int64_t ldP;
+  float dconst;
+  float* pkey;          // partial lists [nq_pad][nslab_total][K], as ScanArgs
+  float* paux;
+  int* prow;
+  int nslab_total;
+  int slab_off;
+  int K;
+};
+// live flags of all leaf-class rows, the two ascending row lists with their counts
+// (counts2[0] isotropic, [1] anisotropic) and the number of allowed sentences in the tree;
+// bc: scratch of ceil(max segment / 1024) ints
+hipError_t launch_mask_build(const uint32_t* bits, const int64_t* sent_ptr, const int64_t* sent_ids, const int* flags,
+                             int NL_iso, int NL_an, uint8_t* live, int* rows_iso, int* rows_an, int* bc,
+                             unsigned long long* n_allowed, int* counts2, hipStream_t s);
+// iso: A = the row-major fp32 copy Mf [row][DP]; else A / B dim-major [DP][ld].  shq (small
+// calls): the workgroup's waves share 16 queries and split the rows, else they share the rows
+// and own 16 queries each
+constexpr int mask_scan_tile(bool shq) { return shq ? 256 : 64; }             // list entries per workgroup step
+constexpr int mask_scan_lists(bool shq) { return shq ? kWavesPerWG : 1; }     // partial lists per slab and query
+hipError_t launch_mask_scan(bool iso, int kl, bool shq, const float* X, const float* A, const float* B,
+                            const MaskScanArgs& a, int nslab, hipStream_t s);
+hipError_t launch_mask_merge_expand(const float* pkey, const float* paux, const int* prow, int nq, int nent, int K,
+                                    int k, const int64_t* sent_ptr, const int64_t* sent_ids, const uint32_t* bits,
+                                    int64_t* ids, float* scores, hipStream_t s);
+hipError_t launch_mask_overfetch(const int64_t* tid, const float* ts, int nq, int kp, int k, const uint32_t* bits,
+                                 int64_t n_allowed, int64_t* ids, float* scores, int* flag, hipStream_t s);
+hipError_t launch_mask_kill(float* rowkey, int64_t ld, int nq, int NL, const uint8_t* live, hipStream_t s);
+hipError_t launch_mask_expand(const float* okey, const int* orow, int nq, int K, int k, const int64_t* sent_ptr,
+                              const int64_t* sent_ids, const uint32_t* bits, int64_t* ids, float* scores,
+                              hipStream_t s);
+hipError_t launch_mask_fill(int64_t* ids, float* scores, int64_t n, hipStream_t s);
+
 }  // namespace cwq
 
 #include <vector>

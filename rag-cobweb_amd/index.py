@@ -88,6 +88,78 @@ class CompactVar:
         return self.row[i].expand(self.shape[1])
 
 
+def pack_sentence_bits(allowed, n_sent):
+    """The bitset cwq_mask_create reads, as an int32 tensor of ceil(n_sent / 32) words on the
+    device `allowed` is on (the CPU for arrays and lists): bit (s % 32) of word (s // 32), least
+    significant bit first, set = sentence s is allowed (numpy.packbits(..., bitorder="little")
+    read as little-endian uint32).  `allowed`: a bool tensor / ndarray / list of length n_sent,
+    or an integer tensor / ndarray / list of sentence ids (duplicates are fine).  ValueError for
+    a bool mask of another length and for an id outside [0, n_sent)."""
+    n_sent = int(n_sent)
+    if not torch.is_tensor(allowed):
+        a = np.asarray(allowed)
+        if a.size == 0 and a.dtype != np.bool_:
+            a = a.astype(np.int64)
+        allowed = torch.from_numpy(np.ascontiguousarray(a))
+    a = allowed.detach().reshape(-1)
+    if a.dtype == torch.bool:
+        if a.numel() != n_sent:
+            raise ValueError(f"a bool mask must have one entry per sentence: got {a.numel()}, the index has {n_sent}")
+        flags = a
+    elif a.dtype.is_floating_point or a.dtype.is_complex:
+        raise ValueError("allowed must be a bool mask or integer sentence ids")
+    else:
+        ids = a.to(torch.int64)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_sent):
+            raise ValueError(f"sentence ids must be in [0, {n_sent})")
+        flags = torch.zeros(n_sent, dtype=torch.bool, device=ids.device)
+        flags[ids] = True
+    words = (n_sent + 31) // 32
+    pad = torch.zeros(words * 32, dtype=torch.int64, device=flags.device)
+    pad[:n_sent] = flags
+    w = (pad.view(words, 32) << torch.arange(32, dtype=torch.int64, device=flags.device)).sum(1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+class SentenceMask:
+    """An allowed-sentence set of one CobwebIndex (a cwq_mask handle; no reference counterpart):
+    made by CobwebIndex.sentence_mask, passed to score_topk(mask=...), reusable across calls and
+    streams.  It keeps its index alive (an index closed meanwhile is destroyed when the last of
+    its masks is).  info: allowed sentences that are in the tree, live isotropic / anisotropic
+    rows, device bytes."""
+
+    def __init__(self, index, allowed):
+        self._h = ctypes.c_void_p()
+        self._index = None
+        bits = pack_sentence_bits(allowed, index.n_sent).to(index.device).contiguous()
+        h = ctypes.c_void_p()
+        with torch.cuda.device(index.device):
+            check(index._L.cwq_mask_create(index._h, _ptr(bits) if bits.numel() else None, index.n_sent,
+                                           _stream(index.device), ctypes.byref(h)))
+        self._h = h
+        self._index = index
+        index._pin()
+        out = np.zeros(4, np.int64)
+        check(index._L.cwq_mask_info(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        self.info = dict(zip(["allowed", "live_iso_rows", "live_aniso_rows", "device_bytes"], (int(v) for v in out)))
+
+    @property
+    def closed(self):
+        return not (self._h and self._h.value)
+
+    def close(self):
+        if not self.closed:
+            self._index._L.cwq_mask_destroy(self._h)
+            self._h = ctypes.c_void_p()
+            self._index._unpin()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CobwebIndex:
     """Immutable flattened tree on one GPU.
 
@@ -274,11 +346,27 @@ class CobwebIndex:
             raise ValueError(f"queries must be [nq, {self.dim}]")
         return q.to(self.device).contiguous()
 
-    def score_topk(self, q, k):
+    def sentence_mask(self, allowed):
+        """A SentenceMask of this index: `allowed` is a bool tensor / ndarray of length n_sent
+        or an integer tensor / list of sentence ids (pack_sentence_bits)."""
+        return SentenceMask(self, allowed)
+
+    def last_mask_stats(self):
+        """The last score_topk(mask=...) call (cwq_last_mask_stats): the path taken (1 over-fetch,
+        2 gathered scan, 3 sort for k > 64), the over-fetch k', the queries the over-fetch left
+        short (redone by the gathered scan), the mask's live rows."""
+        out = np.zeros(4, np.int64)
+        check(self._L.cwq_last_mask_stats(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return {"path": int(out[0]), "overfetch_k": int(out[1]), "redone_queries": int(out[2]), "live_rows": int(out[3])}
+
+    def score_topk(self, q, k, mask=None):
         """Top-k sentence ids/scores per query ("Cobweb Fast", A6).  One call per query is
         the reference harness's mode (benchmark_utils.py:801-805), so a float32 [nq, dim]
         tensor already on the index device goes straight through: no conversion, no device
-        switch (the library selects its device itself), the raw current stream."""
+        switch (the library selects its device itself), the raw current stream.
+        mask (a SentenceMask of this index): the ranking restricted to its allowed sentences --
+        the full ranking with the others removed, cut to k, padded with -1 / -inf
+        (cwq_score_topk_masked)."""
         if not (type(q) is torch.Tensor and q.dtype == torch.float32 and q.device == self.device and q.dim() == 2
                 and q.shape[1] == self.dim and q.is_contiguous()):
             q = self._queries(q)
@@ -286,6 +374,12 @@ class CobwebIndex:
         k = int(k)
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        if mask is not None:
+            if not isinstance(mask, SentenceMask) or mask.closed:
+                raise ValueError("mask must be an open SentenceMask (CobwebIndex.sentence_mask)")
+            check(self._L.cwq_score_topk_masked(self._h, mask._h, q.data_ptr(), nq, k, ids.data_ptr(),
+                                                scores.data_ptr(), _stream_raw(self.device.index)))
+            return ids, scores
         check(self._L.cwq_score_topk(self._h, q.data_ptr(), nq, k, ids.data_ptr(), scores.data_ptr(),
                                      _stream_raw(self.device.index)))
         return ids, scores

@@ -30,7 +30,7 @@ import random
 import numpy as np
 import torch
 
-from .index import CobwebIndex
+from .index import CobwebIndex, SentenceMask
 from .tree import CobwebTree
 
 MAX_INIT_SEARCH = 100000   # CobwebWrapper.py:24
@@ -273,13 +273,45 @@ class CobwebWrapper:
             return emb.detach().to(self.device, torch.float32).reshape(-1)
         return torch.as_tensor(np.asarray(emb, dtype=np.float32), device=self.device).reshape(-1)
 
-    def cobweb_predict_indexed(self, input, k=5, return_ids=False, is_embedding=False):
-        """CobwebWrapper.py:210-265 ("Cobweb Fast")."""
+    def sentence_mask(self, allowed):
+        """An allowed-sentence set to pass as `allowed=` to the Fast calls again and again (no
+        reference counterpart): a bool tensor / array with one entry per sentence, or sentence
+        ids.  It belongs to the current prediction index: after add_sentences, set_level_weights
+        or force_rebuild_index make a new one."""
+        self.build_prediction_index()
+        return self._index.sentence_mask(allowed)
+
+    def _mask_for(self, allowed):
+        """(mask, made here) for a call's `allowed`: a SentenceMask of the current index as it
+        is, anything else through sentence_mask (the caller closes that one after its call)."""
+        if isinstance(allowed, SentenceMask):
+            if allowed.closed:
+                raise ValueError("the SentenceMask is closed")
+            if allowed._index is not self._index:
+                raise ValueError("the SentenceMask belongs to an earlier prediction index: the index was rebuilt "
+                                 "since (add_sentences, set_level_weights or force_rebuild_index); make a new "
+                                 "one with sentence_mask()")
+            return allowed, False
+        return self._index.sentence_mask(allowed), True
+
+    def cobweb_predict_indexed(self, input, k=5, return_ids=False, is_embedding=False, allowed=None):
+        """CobwebWrapper.py:210-265 ("Cobweb Fast").  allowed (no reference counterpart): a
+        SentenceMask, a bool mask over the sentences or sentence ids -- only these sentences
+        are ranked."""
         self.build_prediction_index()
         n = self._index.n_sent if self._leaf_to_path_indices is None else len(self._leaf_to_path_indices)
         if n == 0:
             return []
         emb = input if is_embedding else self.encode_func([input])[0]
+        if allowed is not None:
+            mask, mine = self._mask_for(allowed)
+            try:
+                ids, _ = self._index.score_topk(self._embed(emb, True)[None, :], min(k, n), mask=mask)
+                row = ids[0].tolist()
+            finally:
+                if mine:
+                    mask.close()
+            return [s if return_ids else self.sentences[s] for s in row if 0 <= s < len(self.sentences)]
         if not torch.is_tensor(emb):
             # a host embedding (the harness's numpy query): host memory in and out
             ids, _ = self._index.score_topk_host(np.asarray(emb, dtype=np.float32).reshape(1, -1), min(k, n))
@@ -292,9 +324,11 @@ class CobwebWrapper:
                 out.append(s if return_ids else self.sentences[s])
         return out
 
-    def cobweb_predict_fast(self, input, k=5, return_ids=False, is_embedding=False):
+    def cobweb_predict_fast(self, input, k=5, return_ids=False, is_embedding=False, allowed=None):
         """CobwebWrapper.py:428-433 (alias)."""
-        return self.cobweb_predict_indexed(input, k, return_ids, is_embedding)
+        if allowed is None:
+            return self.cobweb_predict_indexed(input, k, return_ids, is_embedding)
+        return self.cobweb_predict_indexed(input, k, return_ids, is_embedding, allowed=allowed)
 
     def cobweb_rank_scores(self, input, is_embedding=False):
         """CobwebWrapper.py:267-294: [n_sentences] leaf scores.  Differentiable: a tensor
@@ -384,10 +418,19 @@ class CobwebWrapper:
         return results
 
     # batched extensions (the benchmark's unit of work)
-    def cobweb_predict_batch(self, queries, k=5):
-        """[Q, D] queries -> (ids [Q, k] int64 tensor, scores [Q, k] float32), Fast path."""
+    def cobweb_predict_batch(self, queries, k=5, allowed=None):
+        """[Q, D] queries -> (ids [Q, k] int64 tensor, scores [Q, k] float32), Fast path.
+        allowed: as in cobweb_predict_indexed, one set for the whole block (-1 / -inf past the
+        allowed sentences)."""
         self.build_prediction_index()
-        return self._index.score_topk(queries, k)
+        if allowed is None:
+            return self._index.score_topk(queries, k)
+        mask, mine = self._mask_for(allowed)
+        try:
+            return self._index.score_topk(queries, k, mask=mask)
+        finally:
+            if mine:
+                mask.close()
 
     def cobweb_categorize_batch(self, queries, k=5, max_nodes=None):
         """[Q, D] queries -> (node ids [Q, k] BFS order, n_found [Q], log_prob calls [Q])."""
