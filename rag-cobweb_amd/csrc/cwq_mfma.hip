@@ -673,6 +673,8 @@ constexpr int OFF_REC = OFF_PL + FT * 4;  // int4   [kFgCap] record staging
 constexpr int OFF_CNT = OFF_REC + kFgCap * 16;   // int[32]: count, chunk, fill, flush scratch, claim; [16 + wave]:
                                                  // RAW, records in the wave's overflow area
 constexpr int FLDS = OFF_CNT + 128;
+constexpr int kFgStage = FSTAGE / 8 / 16;   // RAW: records of a wave's staging area, its eighth of a stage buffer
+static_assert(kFgStage == 256, "a full 16 x 16 sub-block (4 values x 64 lanes) fits the staging area");
 
 
 // Internal node i, query x (mode 2): lp'(i) = -0.5 (logdet_i + S), S = sum_d w_d (x_d - mu_d)^2
@@ -978,8 +980,10 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
   acc_t acc[8][4];
 #if FG_STAMP
   // diagnostic: per-tile timestamps of wave 0 of workgroups 0..63, tiles 0..15: [wg][tile][8]
-  // (0 setup start, 1 setup barrier passed, 2 K loop done, 3 fast-path test done, 4 slow
-  // path done, 5 flush barrier passed, 6 flush / epilogue done) after the stage stamps
+  // (0 setup start, 1 setup barrier passed, 2 K loop done, 3 fast-path test done (RAW: the
+  // pretest with its staging), 4 slow path done, 5 flush barrier passed (RAW: the fallback
+  // walk's start, in tiles where it ran), 6 flush / epilogue done, 7 RAW: commit done)
+  // after the stage stamps
   unsigned long long* tsp = (a.stamp && blockIdx.x < 64 && tid == 0) ? a.stamp + 16384 + (size_t)blockIdx.x * 128 : nullptr;
 #define FG_TS(k)                                                                  \
   do {                                                                            \
@@ -1102,16 +1106,27 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     //    (I8: the query scales in s_pi / s_pl and the row terms behind FLDS likewise.)
     //  s_cnt[8] (next tile claim): written by thread 0 in setup n, read by all right after
     //    S(n); rewritten in setup n+1, which wave 0 reaches through K loop n (WAR ok).
-    //  s_cnt[0], s_rec (carried record list): appended to by E(n) with LDS atomics.  The
+    //  s_cnt[0], s_rec (carried record list): appended to by E(n) with LDS atomics -- the
+    //    commit's one claim of n_w slots per wave, the fallback walk's claims per record --
+    //    each claimed slot written by its claimant only.  The
     //    count read here after S(n) holds all of E(n-1) and is the same for every thread:
     //    the next append is in E(n), behind the K loop's barriers.  The flush reads s_rec,
     //    and thread 0 clears the count after barrier F, which follows every thread's read
     //    of it; both precede the K loop's barriers and so E(n)'s appends (WAR ok).
     //  s_cnt[1..7] (chunk bookkeeping): written by thread 0 before F, read by all after F
     //    and before the K loop; the next flush is at least one K loop later.
-    //  Stage buffers: E(n) uses the buffer just consumed only when the list is full (the
-    //    wave's overflow area), each wave its own 4 KiB, before it arrives at S(n+1); the
-    //    DMA into that buffer is issued in K loop n+1, after S(n+1) (WAR ok).
+    //  Stage buffers: E(n) uses the buffer just consumed, each wave its own 4 KiB (wrec),
+    //    before it arrives at S(n+1); the DMA into that buffer is issued in K loop n+1, after
+    //    S(n+1) (WAR ok), and its last fragment reads ended (lgkmcnt(0) of the last memory
+    //    section) before the K loop's last barrier.  Within the wave, in program order:
+    //    (1) the pretest's staging (int8) writes wrec[0 .. n_w); (2) a wavefront release / barrier /
+    //    acquire; (3) the commit reads wrec[0 .. n_w) -- copy to s_rec, drain of the part past
+    //    kFgCap -- then a wave barrier and release; (4) the fallback walk, which writes wrec
+    //    from its front again (overflow records) and drains it behind its own fences.  A
+    //    wave's LDS operations complete in order, so each step sees the one before.
+    //  s_cnt[16 + wave] (overflow records in wrec): this wave's only, by the fallback walk;
+    //    0 whenever the walk is not between an overflow append and its drain -- staging and
+    //    commit count in n_w (a scalar register) and never touch it.
     if (RAW) {
       const int cnt = s_cnt[0];
       if (cnt >= kFgCap / 2) flush_records(cnt);   // at least half full: a tile then has kFgCap / 2 slots left
@@ -1357,7 +1372,36 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
       // the four values of a sub-block reduce with v_max3 + v_max).  Every element still
       // gets the scalar form's operations in its order, each rounded once, so the values
       // are pre8's bit for bit (no contraction: pragma below).
-      uint32_t sbm = 0;
+      // Staging.  A flagged sub-block's survivors (p >= 0: the values the flag was formed
+      // from) become finished records {q, row, d, ex} on the spot, while p, t, the query
+      // terms and R_r are in registers: d the dot without the pretest terms and ex the
+      // rounding the accumulator init added to it (fg_bounds2's eextra).  They go to wrec,
+      // the wave's 4 KiB (kFgStage records) of the stage buffer just consumed (the other
+      // instantiations' wsc), free until a wave issues the next tile's first K step -- after
+      // the next setup barrier, which this wave reaches after this epilogue.  The slots come
+      // from the four ballots (n_w, the wave's count, is wave-uniform: scalar), one
+      // ds_write_b128 per surviving lane, no LDS atomic, no LDS read.  A sub-block that does
+      // not fit the area whole is deferred whole to the rolled walk below (todo).  Padding
+      // rows and queries never get here (R0 = -inf / qv = +inf).
+      // I8 only: the bf16 launches measured 2% slower with staging (their pretest is a max and
+      // a compare per sub-block, and the staging branches cost more than the walk of their
+      // few flagged tiles), so the bf16 instantiation defers every flagged sub-block (DESIGN C.1).
+      uint32_t todo = 0;
+      int n_w = 0;
+      int4* const wrec = reinterpret_cast<int4*>(wsc);
+      // (defined outside the pretest's contract(off) block: the staged records and the
+      // walk's get d and ex from the same operations)
+      auto raw_de = [&](float d0, float Rv, float qv, float sx, float& d, float& ex) {
+        if (I8) {
+          d = __fmul_rn(d0, sx);
+          ex = 0x1p-21f * fabsf(d);
+        } else {
+          const float init = Rv - qv;
+          d = d0 - init;
+          ex = a.gamma * fabsf(init) + 0x1p-23f * (fabsf(d0) + fabsf(init));
+        }
+      };
+      const int qb = q0 + wq * 128 + 4 * c16, rb = r0 + wr * 64 + r16;   // the lane's first query and row
       if constexpr (RAW) {
 #pragma clang fp contract(off)
         if constexpr (I8) {
@@ -1389,9 +1433,9 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
           f32x2 qv2[2] = {}, sx2[2] = {};
           if constexpr (I8) {
             const float4 qv4 = *reinterpret_cast<const float4*>(s_qvt + ql);
-            const float4 sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
             qv2[0] = f32x2{qv4.x, qv4.y};
             qv2[1] = f32x2{qv4.z, qv4.w};
+            const float4 sx4 = *reinterpret_cast<const float4*>(s_sx + ql);
             sx2[0] = f32x2{sx4.x, sx4.y};
             sx2[1] = f32x2{sx4.z, sx4.w};
           }
@@ -1408,10 +1452,43 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
               }
             }
             const f32x2 m2 = __builtin_elementwise_max(p[0], p[1]);
-            if (__ballot(__builtin_fmaxf(m2.x, m2.y) >= 0.f) != 0) sbm |= 1u << (jb * 8 + ib);
+            const bool flag = __ballot(__builtin_fmaxf(m2.x, m2.y) >= 0.f) != 0;
+            if constexpr (!I8) {
+              if (flag) todo |= 1u << (jb * 8 + ib);
+              continue;
+            }
+            // (unlikely: the body lies out of line, and an unflagged sub-block -- nine in ten --
+            // falls through one scalar branch that is not taken; with the body in line the
+            // pretest measured 400 cycles longer)
+            if (__builtin_expect(flag, 0)) {
+              const float pj[4] = {p[0].x, p[0].y, p[1].x, p[1].y};
+              unsigned long long bj[4];
+              int need = 0;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                bj[j] = __ballot(pj[j] >= 0.f);
+                need += __builtin_popcountll(bj[j]);
+              }
+              if (n_w + need <= kFgStage) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  if (pj[j] >= 0.f) {
+                    float d, ex;
+                    raw_de(I8 ? __int_as_float(acc[ib][jb][j]) : (float)acc[ib][jb][j], R0[jb], qv2[j >> 1][j & 1],
+                           sx2[j >> 1][j & 1], d, ex);
+                    const int slot = n_w + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bj[j] >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)bj[j], 0u));
+                    wrec[slot] = make_int4(qb + ib * 16 + j, rb + jb * 16, __float_as_int(d), __float_as_int(ex));
+                  }
+                  n_w += __builtin_popcountll(bj[j]);
+                }
+              } else {
+                todo |= 1u << (jb * 8 + ib);
+              }
+            }
           }
         }
-        any = sbm != 0;
+        any = (n_w | (int)todo) != 0;
       } else {
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb)
@@ -1429,23 +1506,49 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
       FG_TS(3);
       if (!any) goto flush;
       if (RAW) {
-        // flagged blocks: the pretest survivors (acc >= 0) go to the record list straight
-        // from the accumulators, as {q, row, d, ex}: d the dot without the pretest terms
-        // and ex the rounding the accumulator init added to it (fg_bounds2's eextra).  No
-        // barrier and, while the list has room, no global load; LDS is read for s_qv only.
-        // Padding rows and queries never get here (R0 = -inf / qv = +inf).
-        // wrec, the wave's overflow area for a full list: its 4 KiB of the stage buffer
-        // just consumed (the other instantiations' wsc), free until a wave issues the next
-        // tile's first K step -- after the next setup barrier, which this wave reaches
-        // after this epilogue.
-        // The walk is one rolled loop over the set bits of the (wave-uniform) mask: a switch
-        // copies the sub-block's four accumulators and its row term out of the register
-        // tile, and one body -- four predicated appends, one overflow drain -- serves all 32
-        // positions (unrolled, the 32 bodies with their drains were 18k instructions).  Each
-        // append claims its slot with an LDS atomic, which the compiler aggregates per wave;
-        // one claim per sub-block from the four ballots measured the same (DESIGN C.1).
-        int4* const wrec = reinterpret_cast<int4*>(wsc);
-        uint32_t todo = sbm;
+        // Records of a full list (slots at or past kFgCap), wrec[k0 .. k1): dense tiles, and
+        // data on which the pretest's margins pass far more than u >= T does: the rigorous
+        // test here (a rolled loop, global loads), so that the direct region takes
+        // candidates only, as on the in-kernel path.
+        auto drain = [&](int k0, int k1) {
+#pragma unroll 1
+          for (int k = k0 + lane; k < k1; k += 64) {
+            const int4 rv = wrec[k];
+            float u, lo;
+            if (fg_raw_bounds<I8>(a, rv.x, rv.y, __int_as_float(rv.z), __int_as_float(rv.w), u, lo)) {
+              const int gs = atomicAdd(&a.gctr[1], 1);
+              if (gs < a.dir_cap) a.rec_dir[gs] = rv;
+              else a.qover[rv.x] = 1;
+            }
+          }
+        };
+        // Commit: the wave's staged records join the carried list with one claim per wave and
+        // tile (one lane, one returning LDS atomic) and one copy; no global load while the list
+        // has room.  Records whose slot is at or past kFgCap stay where they are -- wrec is
+        // the overflow area -- and are drained from there.
+        if (n_w > 0) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the staging writes, before other lanes read them
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          int base = 0;
+          if (lane == 0) base = atomicAdd(&s_cnt[0], n_w);
+          base = __builtin_amdgcn_readfirstlane(base);
+          const int room = max(0, min(n_w, kFgCap - base));
+#pragma unroll 1
+          for (int k = lane; k < room; k += 64) s_rec[base + k] = wrec[k];
+          if (__builtin_expect(room < n_w, 0)) drain(room, n_w);
+          __builtin_amdgcn_wave_barrier();   // the area is read before the walk refills it
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        }
+        FG_TS(7);
+        if (todo) FG_TS(5);
+        // Deferred sub-blocks (the staging area was full: dense tiles, duplicates): one rolled
+        // loop over the set bits of the (wave-uniform) mask: a switch copies the sub-block's
+        // four accumulators and its row term out of the register tile, and one body -- four
+        // predicated appends, one overflow drain -- serves all 32 positions (unrolled, the 32
+        // bodies with their drains were 18k instructions).  Each append claims its slot with
+        // an LDS atomic, which the compiler aggregates per wave.  The list's overflow goes to
+        // wrec from its front, s_cnt[16 + wave] records (0 outside this loop).
 #pragma unroll 1
         while (todo) {
           const int sb = __builtin_ctz(todo);
@@ -1475,16 +1578,8 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (I8 ? pre8(d0j[j], sxj[j], Rv, qvj[j]) >= 0.f : d0j[j] >= 0.f) {
-              const float d0 = d0j[j];
               float d, ex;
-              if (I8) {
-                d = __fmul_rn(d0, sxj[j]);
-                ex = 0x1p-21f * fabsf(d);
-              } else {
-                const float init = Rv - qvj[j];
-                d = d0 - init;
-                ex = a.gamma * fabsf(init) + 0x1p-23f * (fabsf(d0) + fabsf(init));
-              }
+              raw_de(d0j[j], Rv, qvj[j], sxj[j], d, ex);
               const int4 rv = make_int4(q0 + ql + j, r, __float_as_int(d), __float_as_int(ex));
               const int slot = atomicAdd(&s_cnt[0], 1);
               if (slot < kFgCap) {
@@ -1495,23 +1590,10 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
               }
             }
           if (__builtin_expect(__any(ovf), 0)) {
-            // Dense tiles, and data on which the pretest's margins pass far more than
-            // u >= T does: the rigorous test here (a rolled loop, global loads), so that
-            // the direct region takes candidates only, as on the in-kernel path.
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int no = s_cnt[16 + wave];
-#pragma unroll 1
-            for (int k = lane; k < no; k += 64) {
-              const int4 rv = wrec[k];
-              float u, lo;
-              if (fg_raw_bounds<I8>(a, rv.x, rv.y, __int_as_float(rv.z), __int_as_float(rv.w), u, lo)) {
-                const int gs = atomicAdd(&a.gctr[1], 1);
-                if (gs < a.dir_cap) a.rec_dir[gs] = rv;
-                else a.qover[rv.x] = 1;
-              }
-            }
+            drain(0, s_cnt[16 + wave]);
             __builtin_amdgcn_wave_barrier();   // the area is read before it is refilled
             if (lane == 0) s_cnt[16 + wave] = 0;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
