@@ -377,6 +377,49 @@ int cwq_score_topk_masked(cwq_index* idx, const cwq_mask* m, const float* q, int
 int cwq_last_mask_stats(const cwq_index* idx, int64_t* out4);
 
 /*
+ * Per-query masks: one masked call over queries with different allowed sets.
+ * Row i of the result is, bit for bit in ids and scores, what
+ * cwq_score_topk_masked(idx, masks[mask_of_query[i]], q + i * dim, 1, k, ...) returns.
+ *   masks          n_masks masks of this index; a mask may stand in several slots or be unused
+ *   mask_of_query  HOST memory, nq entries in [0, n_masks): the plan is made on the host
+ * For k <= 64 every mask that queries name is classed by cwq_score_topk_masked's rule at the
+ * call's whole nq (CWQ_MASK_PATH forces all masks one way).
+ *   - The over-fetch masks share one unmasked call per width k' in {16, 32, 40, 64} (a
+ *     mask's k' rounded up; a call of <= 64 queries runs one width, its widest) and one
+ *     read-back of the short flags.
+ *   - The queries planned to the gathered scan and the short ones are staged sorted by mask
+ *     and scanned by at most four kernel launches per workspace chunk (segment x form),
+ *     however many masks the call names.
+ *   - Queries of a mask without a live row are -1 / -inf and never scanned.
+ *   - A mask with <= 64 queries that the rule over-fetches as a call of that size, but sends
+ *     to the gathered scan at the whole nq (a batch caps k' at 40), runs as a single-mask
+ *     call of its own inside this call.
+ *   - The loop form: where the gathered scan's own work dwarfs the per-call cost saved (its
+ *     planned row-queries at 14.4 G/s x 768 / DP above 4 x 0.3 ms x masks, constants fitted
+ *     on flat 1M x 768), every mask runs as a single-mask call of its own.
+ *     Stats [1], [4] and [5] then stay 0.
+ * k > 64: the sort path per mask on its gathered queries.  When every query names the same
+ * mask the call is cwq_score_topk_masked itself (same path, same cwq_last_mask_stats).
+ * The rows are the same bits whichever way a mask runs.  Env CWQ_MASK_MULTI_FORM, read per
+ * call: 0 / unset the rules, 1 grouped only, 2 loop form.
+ * The call synchronises `stream`.
+ * CWQ_ERR_ARG with a message, before any device work: a NULL idx / masks / mask_of_query, a
+ * NULL q / ids at nq > 0, n_masks < 1, k <= 0, a NULL entry of masks, a mask built for
+ * another index, an entry of mask_of_query outside [0, n_masks) (the message names the first
+ * such query).  nq == 0 is a no-op.
+ * cwq_last_mask_multi_stats(out8): [queries answered by the over-fetch leg, distinct
+ * over-fetch widths run, queries the over-fetch left short (redone by the gathered scan),
+ * queries planned straight to the gathered scan, gathered-scan kernel launches, gathered-scan
+ * work items (workgroups), distinct masks referenced, queries through the k > 64 sort].
+ * After a multi call cwq_last_mask_stats reports [4, the widest over-fetch width run (0:
+ * none), queries left short, live rows summed over the distinct masks referenced].
+ */
+int cwq_score_topk_masked_multi(cwq_index* idx, const cwq_mask* const* masks, int32_t n_masks,
+                                const int32_t* mask_of_query, const float* q, int64_t nq, int32_t k, int64_t* ids,
+                                float* scores, void* stream);
+int cwq_last_mask_multi_stats(const cwq_index* idx, int64_t* out8);
+
+/*
  * Group pruning of the Fast query (clustered trees whose rows are
  * group-centred, every level weight >= 0): per (query, depth-1 group) a certified upper
  * bound of every key in the group; the exact internal pass runs for each query's best group

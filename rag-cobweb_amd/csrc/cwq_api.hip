@@ -33,7 +33,7 @@ static bool env_set(const char* name) { return getenv(name) != nullptr; }
 #ifndef CWQ_BUILD_ID
 #define CWQ_BUILD_ID "unversioned"
 #endif
-extern "C" int cwq_version(void) { return 300; }
+extern "C" int cwq_version(void) { return 310; }
 // "CWQ_BUILD_ID=<id>" is also searched for in the file by build.py (no dlopen needed)
 static const char kBuildId[] = "CWQ_BUILD_ID=" CWQ_BUILD_ID;
 extern "C" const char* cwq_build_id(void) { return kBuildId + 13; }

@@ -281,8 +281,13 @@ struct cwq_index {
   GrowBuf fb2{GrowBuf::kDevice, 1, "categorize fallback buffers"};   // categorize's filter fallback (its exact re-run uses fb itself)
   // cwq_score_topk_masked, over-fetch path: the unmasked top-k' ids / scores and the per-query
   // short flags (not from `ws`: score_topk_impl carves that anew per chunk)
+  // (cwq_score_topk_masked_multi: the same per width, the gathered queries and the device tables)
   GrowBuf mk{GrowBuf::kDevice, 1 << 16, "masked top-k buffers hipMalloc failed ("};
+  // cwq_score_topk_masked_multi, masks run as calls of their own: one mask's gathered queries
+  // and results (the single-mask call uses mk and fb itself)
+  GrowBuf mg{GrowBuf::kDevice, 1 << 16, "per-query masks: sub-call buffers hipMalloc failed ("};
   int64_t mask_stats[4] = {0, 0, 0, 0};   // cwq_last_mask_stats
+  int64_t mask_multi_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // cwq_last_mask_multi_stats
 
   template <class T>
   int alloc(T** p, size_t n) {
@@ -338,7 +343,7 @@ struct cwq_index {
     if (ws_ev_live) (void)hipEventSynchronize(ws_ev);
     if (ws_ev) (void)hipEventDestroy(ws_ev);
     for (void* p : allocs) (void)hipFree(p);
-    for (GrowBuf* b : {&ws, &fb, &fb2, &mk, &hflags, &hq, &dq, &hout}) b->release();
+    for (GrowBuf* b : {&ws, &fb, &fb2, &mk, &mg, &hflags, &hq, &dq, &hout}) b->release();
   }
 };
 

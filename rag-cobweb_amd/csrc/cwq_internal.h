@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cwq_maskplan.h"
 
 namespace cwq {
 
@@ -1076,6 +1077,28 @@ hipError_t launch_mask_expand(const float* okey, const int* orow, int nq, int K,
                               const int64_t* sent_ids, const uint32_t* bits, int64_t* ids, float* scores,
                               hipStream_t s);
 hipError_t launch_mask_fill(int64_t* ids, float* scores, int64_t n, hipStream_t s);
+
+// ---- per-query masks (cwq_score_topk_masked_multi) ----
+// A mask as the multi kernels see it: its bitset and its allowed sentences in the tree.
+struct MaskSlot {
+  const uint32_t* bits;
+  int64_t n_allowed;
+};
+// The grouped gathered scan: block b of the launch runs work[b] (cwq_maskplan.h; one launch per
+// segment and form).  Of `a` it reads what is the same for every group: DP, seg_base, ld, meta,
+// par, P, ldP, dconst, the list buffers and K.
+hipError_t launch_mask_scan_grouped(bool iso, int kl, bool shq, const float* X, const float* A, const float* B,
+                                    const MaskScanArgs& a, const MaskWork* work, int n_work, hipStream_t s);
+// merge-expand of staged queries mq[0, n): lists and bitset per query, result row mq[i].orig
+hipError_t launch_mask_merge_expand_multi(const float* pkey, const float* paux, const int* prow, const MaskMergeQ* mq,
+                                          int n, int K, int k, const int64_t* sent_ptr, const int64_t* sent_ids,
+                                          int64_t* ids, float* scores, hipStream_t s);
+// over-fetch compaction of gathered queries i < n: mask slots[qslot[i]], result row and flag qorig[i]
+hipError_t launch_mask_overfetch_multi(const int64_t* tid, const float* ts, int n, int kp, int k, const MaskSlot* slots,
+                                       const int* qslot, const int* qorig, int64_t* ids, float* scores, int* flag,
+                                       hipStream_t s);
+// rows idx[0, n) of ids / scores [.][k]: every id -1, every score -inf
+hipError_t launch_mask_fill_rows(int64_t* ids, float* scores, int k, const int* idx, int n, hipStream_t s);
 
 }  // namespace cwq
 

@@ -151,12 +151,24 @@ hipError_t launch_mask_build(const uint32_t* bits, const int64_t* sent_ptr, cons
 // are few).  Grid: slab * n_qblocks + query block (queries fastest, so a tile is read from
 // HBM once and then from L2).
 // ---------------------------------------------------------------------------
+// the planner (cwq_maskplan.h, host only) restates these; scripts/maskplan_check.cpp's bounds
+// proof holds for the kernel only while they agree
+static_assert(kMpXQ == kXQ && kMpWaves == kWavesPerWG, "cwq_maskplan.h: query group / waves per workgroup");
+static_assert(mp_tile(false) == mask_scan_tile(false) && mp_tile(true) == mask_scan_tile(true), "cwq_maskplan.h: tile");
+static_assert(mp_lists(false) == mask_scan_lists(false) && mp_lists(true) == mask_scan_lists(true),
+              "cwq_maskplan.h: lists per slab");
+static_assert(mp_qblock(false) == kXQ * kWavesPerWG && mp_qblock(true) == kXQ, "cwq_maskplan.h: queries per block");
 constexpr int kMsDC = 32;              // dims per staged chunk (DP is a multiple of 32)
 constexpr int kMsStride = kMsDC + 1;   // LDS floats per row
 
-template <bool ISO, int KL, bool SHQ>
+// GRP (the grouped form): the slab, the row list, the queries and the lists come
+// from the workgroup's work item work[blockIdx.x] instead of blockIdx.x and `a` (one launch per
+// segment and form serves every mask of a call); everything else is the same code.
+template <bool ISO, int KL, bool SHQ, bool GRP>
 __global__ __launch_bounds__(256) void mask_scan_kernel(const float* __restrict__ X, const float* __restrict__ A,
-                                                        const float* __restrict__ B, const MaskScanArgs a) {
+                                                        const float* __restrict__ B, const MaskScanArgs a,
+                                                        const MaskWork* __restrict__ work) {
+  const MaskWork* __restrict__ w = GRP ? work + blockIdx.x : nullptr;
   constexpr int TQ = kXQ;
   constexpr int QPR = 64 / KL;
   constexpr int NLR = (TQ + QPR - 1) / QPR;
@@ -167,13 +179,15 @@ __global__ __launch_bounds__(256) void mask_scan_kernel(const float* __restrict_
   __shared__ int srow[ISO ? TILE : 1];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int qb = blockIdx.x % a.n_qblocks;
-  const int slab = blockIdx.x / a.n_qblocks;
-  const int q0 = SHQ ? qb * TQ : (qb * kWavesPerWG + wave) * TQ;
+  const int qb = GRP ? 0 : blockIdx.x % a.n_qblocks;
+  const int slab = GRP ? 0 : blockIdx.x / a.n_qblocks;
+  const int q0 = GRP ? w->q0 + (SHQ ? 0 : wave * TQ) : SHQ ? qb * TQ : (qb * kWavesPerWG + wave) * TQ;
+  const int q_end = GRP ? w->q_end : a.nq;   // the end of the queries that share this row list
   // a wave past the call's queries still helps to stage the tile
-  const int nvq = __builtin_amdgcn_readfirstlane(max(0, min(TQ, a.nq - q0)));
-  const int i_begin = slab * a.rows_per_slab;
-  const int i_end = min(i_begin + a.rows_per_slab, a.n_live);
+  const int nvq = __builtin_amdgcn_readfirstlane(max(0, min(TQ, q_end - q0)));
+  const int i_begin = GRP ? w->i_begin : slab * a.rows_per_slab;
+  const int i_end = GRP ? w->i_end : min(i_begin + a.rows_per_slab, a.n_live);
+  const int* list = GRP ? w->list : a.list;
   const int NV16 = a.DP / 16;
   const int NCH = a.DP / kMsDC;
   const f32x16* __restrict__ xg = reinterpret_cast<const f32x16*>(X) + (size_t)(q0 / kXQ) * NV16 * kXQ;
@@ -194,7 +208,7 @@ __global__ __launch_bounds__(256) void mask_scan_kernel(const float* __restrict_
     for (int l = 0; l < LPL; ++l) {
       trow[l] = SHQ ? wave * kWave + lane : lane + kWave * l;
       vrow[l] = it + trow[l] < i_end;
-      row[l] = a.list[vrow[l] ? it + trow[l] : i_end - 1];   // < the segment's row count
+      row[l] = list[vrow[l] ? it + trow[l] : i_end - 1];   // < the segment's row count
     }
     float acc[LPL][TQ];
 #pragma unroll
@@ -316,8 +330,12 @@ __global__ __launch_bounds__(256) void mask_scan_kernel(const float* __restrict_
     const int gq = qi % QPR;
     const int q = q0 + qi;
     const bool ing = (KL == 64) || ((lane >> 4) == gq);
-    if (q < a.nq && ing && slot < a.K) {
-      const size_t o = ((size_t)q * a.nslab_total + a.slab_off + lst) * a.K + slot;
+    if (q < q_end && ing && slot < a.K) {
+      size_t o;
+      if constexpr (GRP)
+        o = ((size_t)w->lbase + (size_t)(q - w->gq0) * w->lpq + w->lslot + (SHQ ? wave : 0)) * a.K + slot;
+      else
+        o = ((size_t)q * a.nslab_total + a.slab_off + lst) * a.K + slot;
       a.pkey[o] = lk[r];
       a.paux[o] = la[r];
       a.prow[o] = lr[r];
@@ -336,7 +354,7 @@ hipError_t launch_mask_scan(bool iso, int kl, bool shq, const float* X, const fl
       a.slab_off + nslab * mask_scan_lists(shq) > a.nslab_total)
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)((int64_t)nslab * a.n_qblocks)), block(256);
-#define CWQ_MS(ISO_, KL_, SHQ_) hipLaunchKernelGGL((mask_scan_kernel<ISO_, KL_, SHQ_>), grid, block, 0, s, X, A, B, a)
+#define CWQ_MS(ISO_, KL_, SHQ_) hipLaunchKernelGGL((mask_scan_kernel<ISO_, KL_, SHQ_, false>), grid, block, 0, s, X, A, B, a, (const MaskWork*)nullptr)
   if (iso) {
     if (kl == 16) { if (shq) CWQ_MS(true, 16, true); else CWQ_MS(true, 16, false); }
     else { if (shq) CWQ_MS(true, 64, true); else CWQ_MS(true, 64, false); }
@@ -348,23 +366,37 @@ hipError_t launch_mask_scan(bool iso, int kl, bool shq, const float* X, const fl
   return hipGetLastError();
 }
 
+hipError_t launch_mask_scan_grouped(bool iso, int kl, bool shq, const float* X, const float* A, const float* B,
+                                    const MaskScanArgs& a, const MaskWork* work, int n_work, hipStream_t s) {
+  if (n_work <= 0) return hipSuccess;
+  if (a.K < 1 || a.K > kl || a.DP % kMsDC || !work) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)n_work), block(256);
+#define CWQ_MSG(ISO_, KL_, SHQ_) \
+  hipLaunchKernelGGL((mask_scan_kernel<ISO_, KL_, SHQ_, true>), grid, block, 0, s, X, A, B, a, work)
+  if (iso) {
+    if (kl == 16) { if (shq) CWQ_MSG(true, 16, true); else CWQ_MSG(true, 16, false); }
+    else { if (shq) CWQ_MSG(true, 64, true); else CWQ_MSG(true, 64, false); }
+  } else {
+    if (kl == 16) { if (shq) CWQ_MSG(false, 16, true); else CWQ_MSG(false, 16, false); }
+    else { if (shq) CWQ_MSG(false, 64, true); else CWQ_MSG(false, 64, false); }
+  }
+#undef CWQ_MSG
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // merge_expand_kernel with the sentence bitset: the merged top-K rows (all live) expand into
 // their allowed sentences only; a row's sentences keep their ascending order and its score.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mask_merge_expand_kernel(const float* __restrict__ pkey,
-                                                                const float* __restrict__ paux,
-                                                                const int* __restrict__ prow, int nq, int nent, int K,
-                                                                int k, const int64_t* __restrict__ sent_ptr,
-                                                                const int64_t* __restrict__ sent_ids,
-                                                                const uint32_t* __restrict__ bits, int64_t* ids,
-                                                                float* scores) {
-  const int lane = threadIdx.x & 63;
-  const int q = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
-  if (q >= nq) return;
+// one wave: the entries [base, base + nent) of the partial lists into result row q
+__device__ __forceinline__ void mask_merge_expand_one(const float* __restrict__ pkey, const float* __restrict__ paux,
+                                                      const int* __restrict__ prow, size_t base, int nent, int K,
+                                                      int k, const int64_t* __restrict__ sent_ptr,
+                                                      const int64_t* __restrict__ sent_ids,
+                                                      const uint32_t* __restrict__ bits, int64_t* ids, float* scores,
+                                                      int q, int lane) {
   float lk = -CWQ_INF, la = 0.f;
   int lr = 0x7fffffff;
-  const size_t base = (size_t)q * nent;
   for (int e0 = 0; e0 < nent; e0 += kWave) {
     const int e = e0 + lane;
     float ek = -CWQ_INF, ea = 0.f;
@@ -414,6 +446,35 @@ __global__ __launch_bounds__(256) void mask_merge_expand_kernel(const float* __r
   }
 }
 
+__global__ __launch_bounds__(256) void mask_merge_expand_kernel(const float* __restrict__ pkey,
+                                                                const float* __restrict__ paux,
+                                                                const int* __restrict__ prow, int nq, int nent, int K,
+                                                                int k, const int64_t* __restrict__ sent_ptr,
+                                                                const int64_t* __restrict__ sent_ids,
+                                                                const uint32_t* __restrict__ bits, int64_t* ids,
+                                                                float* scores) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  mask_merge_expand_one(pkey, paux, prow, (size_t)q * nent, nent, K, k, sent_ptr, sent_ids, bits, ids, scores, q, lane);
+}
+
+// the grouped form: the lists, the bitset and the result row per staged query
+__global__ __launch_bounds__(256) void mask_merge_expand_multi_kernel(const float* __restrict__ pkey,
+                                                                      const float* __restrict__ paux,
+                                                                      const int* __restrict__ prow,
+                                                                      const MaskMergeQ* __restrict__ mq, int n, int K,
+                                                                      int k, const int64_t* __restrict__ sent_ptr,
+                                                                      const int64_t* __restrict__ sent_ids,
+                                                                      int64_t* ids, float* scores) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const MaskMergeQ m = mq[i];
+  mask_merge_expand_one(pkey, paux, prow, (size_t)m.lfirst * K, m.nlists * K, K, k, sent_ptr, sent_ids, m.bits, ids,
+                        scores, m.orig, lane);
+}
+
 hipError_t launch_mask_merge_expand(const float* pkey, const float* paux, const int* prow, int nq, int nent, int K,
                                     int k, const int64_t* sent_ptr, const int64_t* sent_ids, const uint32_t* bits,
                                     int64_t* ids, float* scores, hipStream_t s) {
@@ -424,18 +485,26 @@ hipError_t launch_mask_merge_expand(const float* pkey, const float* paux, const 
   return hipGetLastError();
 }
 
+hipError_t launch_mask_merge_expand_multi(const float* pkey, const float* paux, const int* prow, const MaskMergeQ* mq,
+                                          int n, int K, int k, const int64_t* sent_ptr, const int64_t* sent_ids,
+                                          int64_t* ids, float* scores, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (K > kWave || K < 1 || !mq) return hipErrorInvalidValue;
+  dim3 grid((unsigned)((n + kWavesPerWG - 1) / kWavesPerWG)), block(256);
+  hipLaunchKernelGGL(mask_merge_expand_multi_kernel, grid, block, 0, s, pkey, paux, prow, mq, n, K, k, sent_ptr,
+                     sent_ids, ids, scores);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // Over-fetch compaction: the allowed entries of an unmasked top-kp result (kp <= 64), in order,
 // cut to k and padded.  flag[q] = the query came up short: fewer than min(k, n_allowed)
 // survived, so allowed sentences rank below the unmasked top-kp (the gathered scan redoes it).
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mask_overfetch_kernel(const int64_t* __restrict__ tid,
-                                                             const float* __restrict__ ts, int nq, int kp, int k,
-                                                             const uint32_t* __restrict__ bits, int64_t n_allowed,
-                                                             int64_t* ids, float* scores, int* flag) {
-  const int lane = threadIdx.x & 63;
-  const int q = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
-  if (q >= nq) return;
+// one wave: row q of the unmasked top-kp result into result row and flag o
+__device__ __forceinline__ void mask_overfetch_one(const int64_t* __restrict__ tid, const float* __restrict__ ts, int q,
+                                                   int kp, int k, const uint32_t* __restrict__ bits, int64_t n_allowed,
+                                                   int64_t* ids, float* scores, int* flag, int o, int lane) {
   int64_t sid = -1;
   float sc = -CWQ_INF;
   if (lane < kp) {
@@ -447,14 +516,39 @@ __global__ __launch_bounds__(256) void mask_overfetch_kernel(const int64_t* __re
   const int pos = __popcll(m & ((1ull << lane) - 1ull));
   const int n = __popcll(m);
   if (ok && pos < k) {
-    ids[(size_t)q * k + pos] = sid;
-    if (scores) scores[(size_t)q * k + pos] = sc;
+    ids[(size_t)o * k + pos] = sid;
+    if (scores) scores[(size_t)o * k + pos] = sc;
   }
   for (int t = n + lane; t < k; t += kWave) {
-    ids[(size_t)q * k + t] = -1;
-    if (scores) scores[(size_t)q * k + t] = -CWQ_INF;
+    ids[(size_t)o * k + t] = -1;
+    if (scores) scores[(size_t)o * k + t] = -CWQ_INF;
   }
-  if (lane == 0) flag[q] = (int64_t)n < (n_allowed < (int64_t)k ? n_allowed : (int64_t)k) ? 1 : 0;
+  if (lane == 0) flag[o] = (int64_t)n < (n_allowed < (int64_t)k ? n_allowed : (int64_t)k) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void mask_overfetch_kernel(const int64_t* __restrict__ tid,
+                                                             const float* __restrict__ ts, int nq, int kp, int k,
+                                                             const uint32_t* __restrict__ bits, int64_t n_allowed,
+                                                             int64_t* ids, float* scores, int* flag) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  mask_overfetch_one(tid, ts, q, kp, k, bits, n_allowed, ids, scores, flag, q, lane);
+}
+
+// the same for gathered queries of several masks: the bitset and n_allowed of query i from
+// slots[qslot[i]], its result row and short flag at its position in the call, qorig[i]
+__global__ __launch_bounds__(256) void mask_overfetch_multi_kernel(const int64_t* __restrict__ tid,
+                                                                   const float* __restrict__ ts, int n, int kp, int k,
+                                                                   const MaskSlot* __restrict__ slots,
+                                                                   const int* __restrict__ qslot,
+                                                                   const int* __restrict__ qorig, int64_t* ids,
+                                                                   float* scores, int* flag) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const MaskSlot m = slots[qslot[i]];
+  mask_overfetch_one(tid, ts, i, kp, k, m.bits, m.n_allowed, ids, scores, flag, qorig[i], lane);
 }
 
 hipError_t launch_mask_overfetch(const int64_t* tid, const float* ts, int nq, int kp, int k, const uint32_t* bits,
@@ -462,6 +556,17 @@ hipError_t launch_mask_overfetch(const int64_t* tid, const float* ts, int nq, in
   if (kp > kWave || kp < 1) return hipErrorInvalidValue;
   dim3 grid((unsigned)((nq + kWavesPerWG - 1) / kWavesPerWG)), block(256);
   hipLaunchKernelGGL(mask_overfetch_kernel, grid, block, 0, s, tid, ts, nq, kp, k, bits, n_allowed, ids, scores, flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_overfetch_multi(const int64_t* tid, const float* ts, int n, int kp, int k, const MaskSlot* slots,
+                                       const int* qslot, const int* qorig, int64_t* ids, float* scores, int* flag,
+                                       hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (kp > kWave || kp < 1) return hipErrorInvalidValue;
+  dim3 grid((unsigned)((n + kWavesPerWG - 1) / kWavesPerWG)), block(256);
+  hipLaunchKernelGGL(mask_overfetch_multi_kernel, grid, block, 0, s, tid, ts, n, kp, k, slots, qslot, qorig, ids,
+                     scores, flag);
   return hipGetLastError();
 }
 
@@ -526,6 +631,24 @@ hipError_t launch_mask_fill(int64_t* ids, float* scores, int64_t n, hipStream_t 
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(mask_fill_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, s, ids,
                      scores, n);
+  return hipGetLastError();
+}
+
+// the rows idx[0, n) only (the queries of masks without a live row, among others' queries)
+__global__ void mask_fill_rows_kernel(int64_t* ids, float* scores, int k, const int* __restrict__ idx, int n) {
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < (int64_t)n * k;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const size_t o = (size_t)idx[t / k] * k + t % k;
+    ids[o] = -1;
+    if (scores) scores[o] = -CWQ_INF;
+  }
+}
+
+hipError_t launch_mask_fill_rows(int64_t* ids, float* scores, int k, const int* idx, int n, hipStream_t s) {
+  if (n <= 0 || k <= 0) return hipSuccess;
+  const int64_t tot = (int64_t)n * k;
+  hipLaunchKernelGGL(mask_fill_rows_kernel, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, s,
+                     ids, scores, k, idx, n);
   return hipGetLastError();
 }
 

@@ -1,9 +1,12 @@
-// Masked Fast top-k (no reference counterpart): the cwq_mask handle and
-// cwq_score_topk_masked.  Calls the launch_mask_* kernels (cwq_mask.hip), the exact per-chunk
-// passes and the unmasked Fast call of cwq_api.hip.
+// Masked Fast top-k (no reference counterpart): the cwq_mask handle,
+// cwq_score_topk_masked and cwq_score_topk_masked_multi.
+// Calls the launch_mask_* kernels (cwq_mask.hip), the exact per-chunk passes and the unmasked
+// Fast call of cwq_api.hip.
 #include <atomic>
+#include <map>
 
 #include "cwq_handle.h"
+#include "cwq_maskplan.h"
 
 namespace cwq {
 uint64_t next_index_serial() {
@@ -31,7 +34,8 @@ constexpr int kMaskMaxKp = 64;        // kFiltMaxK: the unmasked filter paths se
 constexpr int kMaskMaxKpBatch = 40;   // calls of more than kMaskSmallQ queries
 constexpr int kMaskSmallQ = kStreamMaxQ;   // up to here the unmasked call is the stream filter's
 constexpr double kMaskSlack = 2.0;
-// the gathered scan's partial lists per query, at most (per segment)
+// the single-mask gathered scan's partial lists per query and segment, at most (the grouped
+// scan's planner caps both segments together at kMpMaxSlabs, the same number)
 constexpr int kMaskMaxSlabs = 2048;
 
 int mask_path_env() {
@@ -51,7 +55,7 @@ int overfetch_kp(const cwq_index* ix, const cwq_mask* m, int k, int64_t nq) {
 }
 
 // small calls take the gathered scan's shared-query form (the waves of a workgroup split the rows)
-constexpr int kMaskShqMaxQ = 32;
+constexpr int kMaskShqMaxQ = kMpShqMaxQ;
 
 // slabs of a segment's row list: enough workgroups for ~4 per CU, whole tiles
 void slab_split(const cwq_index* ix, int n_live, int n_qblocks, bool shq, int& nslab, int& rps) {
@@ -176,6 +180,9 @@ int redo_short(cwq_index* ix, const cwq_mask* m, const float* q, const std::vect
 
 }  // namespace
 
+static int masked_single_locked(cwq_index* ix, const cwq_mask* m, const float* q, int64_t nq, int32_t k, int64_t* ids,
+                                float* scores, hipStream_t s);
+
 extern "C" int cwq_mask_create(cwq_index* ix, const uint32_t* bits, int64_t n_sent, void* stream, cwq_mask** out) {
   if (!ix || !out || (!bits && n_sent > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
   *out = nullptr;
@@ -252,6 +259,14 @@ extern "C" int cwq_score_topk_masked(cwq_index* ix, const cwq_mask* m, const flo
   topk_begin(ix);
   for (int64_t& t : ix->mask_stats) t = 0;
   if (call.rc) return call.rc;
+  return masked_single_locked(ix, m, q, nq, k, ids, scores, s);
+}
+
+// cwq_score_topk_masked under the handle's lock (the multi call runs it per mask where a mask is
+// better served as a call of its own; it starts the last call's stats anew each time)
+static int masked_single_locked(cwq_index* ix, const cwq_mask* m, const float* q, int64_t nq, int32_t k, int64_t* ids,
+                                float* scores, hipStream_t s) {
+  for (int64_t& t : ix->mask_stats) t = 0;
   // the path: k > 64 always sorts; else CWQ_MASK_PATH (read per call) or the rule
   const int forced = mask_path_env();
   int kp = overfetch_kp(ix, m, k, nq);
@@ -294,5 +309,468 @@ extern "C" int cwq_score_topk_masked(cwq_index* ix, const cwq_mask* m, const flo
 extern "C" int cwq_last_mask_stats(const cwq_index* ix, int64_t* out) {
   if (!ix || !out) return fail(CWQ_ERR_ARG, "NULL argument");
   for (int i = 0; i < 4; ++i) out[i] = ix->mask_stats[i];
+  return CWQ_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Per-query masks (cwq_score_topk_masked_multi)
+// ---------------------------------------------------------------------------
+namespace {
+
+// Over-fetch widths of the multi call: a mask's k' is rounded up to the next of these, and each
+// width runs one unmasked call over the queries of all its masks.  They follow the unmasked
+// filter's cost steps (the comment at kMaskMaxKp): up to 32 a batch costs about the same, 40 is
+// the batch cap, 64 the cap of calls of <= kMaskSmallQ queries.
+constexpr int kMultiWidths[4] = {16, 32, 40, 64};
+int multi_width(int kp) {
+  for (int w : kMultiWidths)
+    if (kp <= w) return w;
+  return kMaskMaxKp;
+}
+
+struct MultiGroup {        // one distinct mask of the call
+  const cwq_mask* m;
+  std::vector<int> qi;     // its queries (positions in the call), ascending
+  int width = 0;           // its over-fetch width; 0: none
+  int kp = 0;              // the k' the rule gave it
+  std::vector<int> scan;   // its queries for the gathered scan (planned there, or left short)
+  bool own = false;        // it runs as a single-mask call of its own (masked_multi_impl)
+};
+
+// The device tables of one phase, packed on the host and sent with one copy: add() returns a
+// table's offset (256-byte aligned) in the device region the blob is sent to.
+struct Blob {
+  std::vector<char> h;
+  template <class T>
+  size_t add(const std::vector<T>& v) {
+    const size_t o = (h.size() + 255) & ~size_t(255);
+    h.resize(o + v.size() * sizeof(T));
+    if (!v.empty()) memcpy(h.data() + o, v.data(), v.size() * sizeof(T));
+    return o;
+  }
+};
+// The blobs of a call (pageable host memory): alive until the call has synchronised its stream.
+struct Uploads {
+  hipStream_t s;
+  std::vector<std::unique_ptr<Blob>> keep;
+  Blob& blob() {
+    keep.emplace_back(new Blob());
+    return *keep.back();
+  }
+  hipError_t send(const Blob& b, void* dst) {
+    return b.h.empty() ? hipSuccess : hipMemcpyAsync(dst, b.h.data(), b.h.size(), hipMemcpyHostToDevice, s);
+  }
+};
+
+bool mask_of_index(const cwq_index* ix, const cwq_mask* m) {
+  return m->serial == ix->serial && m->n_sent == ix->n_sent && m->NL_iso == ix->NL_iso && m->NL_an == ix->NL_an;
+}
+
+// The grouped gathered scan of every group's `scan` queries (k <= 64): the plan of
+// cwq_maskplan.h, then per chunk the staged queries, one exact internal pass, one scan launch
+// per (segment, form) and one grouped merge.  tq: room for max_slots staged queries (the
+// handle's mk buffer).
+int multi_gathered(cwq_index* ix, const std::vector<MultiGroup>& gs, const float* q, int32_t k, int64_t* ids,
+                   float* scores, float* tq, int64_t max_slots, Uploads& up, hipStream_t s) {
+  const int K = std::min<int>(k, 64);
+  const int kl = K <= 16 ? 16 : 64;
+  std::vector<int> gidx;   // planner group -> gs
+  std::vector<MpGroup> pg;
+  for (size_t g = 0; g < gs.size(); ++g) {
+    if (gs[g].scan.empty()) continue;
+    gidx.push_back((int)g);
+    pg.push_back(MpGroup{(int)gs[g].scan.size(), {gs[g].m->n_iso, gs[g].m->n_an}});
+  }
+  if (pg.empty()) return CWQ_OK;
+  MpParams p;
+  p.cus = ix->cus;
+  p.K = K;
+  p.entry_bytes = 12;
+  p.slot_bytes = (chunk_bytes(ix, 2 * kQPad, false) - chunk_bytes(ix, kQPad, false)) / kQPad;
+  p.budget = (size_t)chunk_queries(ix, INT_MAX, 0, false) * p.slot_bytes;
+  MaskPlan plan;
+  mask_plan(pg, p, plan);
+  auto table_bytes = [](const MpChunk& ch) {
+    size_t b = round_up((int64_t)(ch.queries.size() * sizeof(MaskMergeQ)), 256) + round_up((int64_t)ch.n_slots * 8, 256);
+    for (int sg = 0; sg < 2; ++sg)
+      for (int f = 0; f < 2; ++f) b += round_up((int64_t)(ch.work[sg][f].size() * sizeof(MaskWork)), 256);
+    return b + 8 * 256;
+  };
+  size_t need = 0;
+  for (const MpChunk& ch : plan.chunks) {
+    if (ch.n_slots > max_slots) return fail(CWQ_ERR_HIP, "masked multi: staged queries past the buffer (internal error)");
+    need = std::max(need, chunk_bytes(ix, round_up(ch.n_slots, kQPad), false) + 64 * 256 +
+                              (size_t)ch.n_lists * K * 12 + table_bytes(ch));
+  }
+  int rc;
+  if ((rc = ix->reserve(need))) return rc;
+  for (MpChunk& ch : plan.chunks) {
+    // the chunk's tables: the staged queries' positions in the call -- sorted by group, each piece
+    // from a kXQ boundary; a gap repeats the piece's last query (no workgroup computes it: nvq
+    // stops at the piece's end) -- the work items with their row lists, the merge's queries
+    std::vector<int64_t> src((size_t)ch.n_slots);
+    for (const MpPiece& pc : ch.pieces) {
+      const std::vector<int>& sq = gs[gidx[pc.group]].scan;
+      const int n = pc.qb - pc.qa, slots = (int)round_up(n, kMpXQ);
+      for (int j = 0; j < slots; ++j) src[pc.slot + j] = sq[pc.qa + std::min(j, n - 1)];
+    }
+    Blob& tb = up.blob();
+    const size_t o_src = tb.add(src);
+    size_t o_w[2][2];
+    for (int sg = 0; sg < 2; ++sg)
+      for (int f = 0; f < 2; ++f) {
+        for (MaskWork& it : ch.work[sg][f])
+          it.list = sg ? gs[gidx[it.group]].m->rows_an : gs[gidx[it.group]].m->rows_iso;
+        o_w[sg][f] = tb.add(ch.work[sg][f]);
+      }
+    for (MaskMergeQ& mq : ch.queries) {
+      const MultiGroup& g = gs[gidx[mq.group]];
+      mq.bits = g.m->bits;
+      mq.orig = g.scan[mq.gidx];
+    }
+    const size_t o_mq = tb.add(ch.queries);
+    // the whole carve, checked against the reservation before anything is launched
+    Bump b(ix->ws.p, ix->ws.size);
+    Chunk c;
+    carve_chunk(ix, b, c, ch.n_slots, false);
+    const size_t nent = (size_t)std::max<int64_t>(1, ch.n_lists) * K;
+    float* pkey = b.take<float>(nent);
+    float* paux = b.take<float>(nent);
+    int* prow = b.take<int>(nent);
+    char* dtab = b.take<char>(tb.h.size());
+    if (b.off > ix->ws.size) return fail(CWQ_ERR_HIP, "masked multi: workspace estimate too small (internal error)");
+    HIPCHK(up.send(tb, dtab));
+    HIPCHK(launch_copy_rows(q, ix->D, (const int64_t*)(dtab + o_src), tq, ix->D, nullptr, ch.n_slots, ix->D, s));
+    HIPCHK(launch_pad_queries(tq, ch.n_slots, ix->D, c.X, c.nq_pad, ix->DP, s));
+    if ((rc = run_internal(ix, c, s, false, tq, -1))) return rc;   // exact prefixes, once for every group
+    MaskScanArgs a;
+    memset(&a, 0, sizeof(a));
+    a.DP = ix->DP;
+    a.nq = ch.n_slots;
+    a.P = c.P ? c.P : ix->dummy;
+    a.ldP = std::max(ix->NI, 1);
+    a.dconst = 0.f;
+    a.pkey = pkey;
+    a.paux = paux;
+    a.prow = prow;
+    a.K = K;
+    for (int sg = 0; sg < 2; ++sg) {
+      a.seg_base = sg ? ix->NL_iso : 0;
+      a.ld = sg ? ix->ld_an : 0;
+      a.meta = ix->row_meta + a.seg_base;
+      a.par = ix->row_par + a.seg_base;
+      for (int f = 0; f < 2; ++f) {
+        const std::vector<MaskWork>& w = ch.work[sg][f];
+        if (w.empty()) continue;
+        HIPCHK(launch_mask_scan_grouped(sg == 0, kl, f == 1, c.X, sg ? ix->an_A : ix->iso_Mf, sg ? ix->an_B : nullptr, a,
+                                        (const MaskWork*)(dtab + o_w[sg][f]), (int)w.size(), s));
+        ix->mask_multi_stats[4] += 1;
+        ix->mask_multi_stats[5] += (int64_t)w.size();
+      }
+    }
+    HIPCHK(launch_mask_merge_expand_multi(pkey, paux, prow, (const MaskMergeQ*)(dtab + o_mq), (int)ch.queries.size(), K, k, ix->sent_ptr,
+                                          ix->sent_ids, ids, scores, s));
+  }
+  return CWQ_OK;
+}
+
+// The loop form: where the gathered scan's own work dwarfs what one call over all masks saves --
+// the fixed cost of a single-mask call, kLoopCallMs each -- the masks run one after another
+// through the single-mask call, each with the slab split and path of a call of its own.
+// Work: the row-queries planned to the gathered scan over its rate.  The constants are fitted
+// to one shape, C3 (flat 1M x 768 on MI355X, profiles/maskmulti_probe_c3.log): 0.28 - 0.4 ms per
+// call in a loop over 1,000 masks; 14.4 G row-queries/s at DP = 768, taken as inversely
+// proportional to DP (the scan's arithmetic and bytes per row-query are); the grouped form lost
+// 2 - 50% from a work / saving ratio of 4.2 up (16 and 128 masks x 10,000 queries at allowed
+// fraction 0.1 - 0.5) and won from 2.7 down.  Other devices and shapes have not been measured.
+constexpr double kLoopCallMs = 0.3, kLoopScanRqPerMs768 = 14.4e6, kLoopRatio = 4.0;
+// CWQ_MASK_MULTI_FORM, read per call: 1 grouped only (no loop form, no masks as calls of their
+// own), 2 loop form, else the rules
+int multi_form_env() {
+  const char* e = getenv("CWQ_MASK_MULTI_FORM");
+  const int v = e && *e ? atoi(e) : 0;
+  return v == 1 || v == 2 ? v : 0;
+}
+bool multi_loop_form(const cwq_index* ix, const std::vector<MultiGroup>& gs) {
+  if (multi_form_env()) return multi_form_env() == 2;
+  if (mask_path_env()) return false;   // a forced path is a test of that path, grouped
+  double rq = 0;
+  for (const MultiGroup& g : gs)
+    if (!g.width && !g.own) rq += (double)g.qi.size() * ((double)g.m->n_iso + g.m->n_an);
+  const double rq_per_ms = kLoopScanRqPerMs768 * 768.0 / (double)std::max(ix->DP, 1);
+  return rq / rq_per_ms > kLoopRatio * kLoopCallMs * (double)gs.size();
+}
+
+// Masks as single-mask calls of their own, one after another (every mask with a live row: the
+// loop form; else those marked `own`): the mask's queries gathered into the handle's mg buffer,
+// masked_single_locked, the rows scattered back.  Counts what each sub-call did into the multi
+// stats [0], [2], [3]; acc: the widest k' and the short queries, for cwq_last_mask_stats.
+int multi_own_calls(cwq_index* ix, const std::vector<MultiGroup>& gs, bool all, const float* q, int64_t nq, int32_t k,
+                    int64_t* ids, float* scores, int64_t acc[2], Uploads& up, hipStream_t s) {
+  int64_t* st = ix->mask_multi_stats;
+  int64_t nmax = 0;
+  std::vector<int64_t> idx;   // the sub-calls' queries (positions in the call), mask after mask: one upload
+  for (const MultiGroup& g : gs)
+    if ((all || g.own) && g.m->n_iso + g.m->n_an > 0) {
+      nmax = std::max<int64_t>(nmax, (int64_t)g.qi.size());
+      idx.insert(idx.end(), g.qi.begin(), g.qi.end());
+    }
+  if (nmax == 0) return CWQ_OK;
+  const int64_t D = ix->D;
+  const size_t o_idx = 0, o_tq = o_idx + round_up((int64_t)idx.size() * 8, 256), o_tid = o_tq + round_up(nmax * D * 4, 256),
+               o_ts = o_tid + round_up(nmax * k * 8, 256), tot = o_ts + round_up(nmax * k * 4, 256);
+  int rc;
+  if ((rc = ix->mg.reserve(tot, ix->busy()))) return rc;
+  char* mg = ix->mg.as<char>();
+  Blob& tb = up.blob();
+  tb.add(idx);
+  HIPCHK(up.send(tb, mg + o_idx));
+  const int64_t* didx = (const int64_t*)(mg + o_idx);
+  float* tq = (float*)(mg + o_tq);
+  int64_t* tid = (int64_t*)(mg + o_tid);
+  float* ts = (float*)(mg + o_ts);
+  // the buffers are reused from mask to mask in stream order: no synchronisation in between
+  for (const MultiGroup& g : gs) {
+    if (!(all || g.own) || g.m->n_iso + g.m->n_an == 0) continue;
+    const int64_t n = (int64_t)g.qi.size();
+    HIPCHK(launch_copy_rows(q, D, didx, tq, D, nullptr, n, D, s));
+    scan_cfg_begin(n);   // the sub-call's own scan configuration
+    rc = masked_single_locked(ix, g.m, tq, n, k, tid, ts, s);
+    scan_cfg_begin(nq);
+    if (rc) return rc;
+    HIPCHK(launch_copy_rows(tid, 2 * (int64_t)k, nullptr, ids, 2 * (int64_t)k, didx, n, 2 * (int64_t)k, s));
+    if (scores) HIPCHK(launch_copy_rows(ts, k, nullptr, scores, k, didx, n, k, s));
+    // as between two calls: the next sub-call waits for this one's work only if it has to free
+    // and grow one of the handle's buffers (cwq_index::busy)
+    if ((rc = ix->ws_end(s))) return rc;
+    didx += n;
+    if (ix->mask_stats[0] == 1) {
+      st[0] += n - ix->mask_stats[2];
+      st[2] += ix->mask_stats[2];
+      acc[0] = std::max(acc[0], ix->mask_stats[1]);
+      acc[1] += ix->mask_stats[2];
+    } else {
+      st[3] += n;
+    }
+  }
+  return CWQ_OK;
+}
+
+// The multi call under the handle's lock.  order: the queries counting-sorted by distinct mask;
+// gs: the distinct masks that queries name.
+int masked_multi_impl(cwq_index* ix, std::vector<MultiGroup>& gs, const float* q, int64_t nq, int32_t k, int64_t* ids,
+                      float* scores, hipStream_t s) {
+  int64_t* st = ix->mask_multi_stats;
+  Uploads up{s, {}};
+  int rc;
+  // ---- masks without a live row: -1 / -inf, never scanned ----
+  std::vector<int> fill;
+  int64_t live = 0;
+  for (MultiGroup& g : gs) {
+    live += (int64_t)g.m->n_iso + g.m->n_an;
+    if (g.m->n_iso + g.m->n_an == 0) fill.insert(fill.end(), g.qi.begin(), g.qi.end());
+  }
+  ix->mask_stats[0] = 4;
+  ix->mask_stats[3] = live;
+  const int64_t D = ix->D;
+  Blob& tb = up.blob();   // the tables of this phase, sent with one copy
+  const size_t o_fill = tb.add(fill);
+  if (k > 64) {
+    // the sort path per mask on its gathered sub-batch (rare, and a full sort per query anyway)
+    if ((rc = ix->mk.reserve(tb.h.size() + 256, ix->busy()))) return rc;
+    HIPCHK(up.send(tb, ix->mk.p));
+    HIPCHK(launch_mask_fill_rows(ids, scores, k, (const int*)(ix->mk.as<char>() + o_fill), (int)fill.size(), s));
+    for (MultiGroup& g : gs) {
+      if (g.m->n_iso + g.m->n_an == 0) continue;
+      std::vector<int64_t> qi(g.qi.begin(), g.qi.end());
+      if ((rc = redo_short(ix, g.m, q, qi, k, ids, scores, s))) return rc;
+      st[7] += (int64_t)qi.size();
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return CWQ_OK;
+  }
+  // ---- the class of every mask, by the single-mask rule at the call's whole nq ----
+  const int forced = mask_path_env();
+  int widths[4] = {kMultiWidths[0], kMultiWidths[1], kMultiWidths[2], kMultiWidths[3]};
+  int64_t n_w[4] = {0, 0, 0, 0}, n_ov = 0, n_ovw = 0, n_scan_max = 0;
+  int n_groups_scan = 0, w_max = 0;
+  for (MultiGroup& g : gs) {
+    if (g.m->n_iso + g.m->n_an == 0) continue;
+    int kp = overfetch_kp(ix, g.m, k, nq);
+    const int path = forced ? forced : kp > 0 ? 1 : 2;
+    if (path == 1 && kp == 0) kp = kMaskMaxKp;
+    g.width = path == 1 ? multi_width(kp) : 0;
+    g.kp = path == 1 ? kp : 0;
+    w_max = std::max(w_max, g.kp);
+    // The rule at the whole nq caps a batch's k' at kMaskMaxKpBatch; a mask with <= kMaskSmallQ
+    // queries of its own that the rule over-fetches as a call of that size (cap kMaskMaxKp)
+    // would go to the gathered scan over most of the corpus here.  It runs as a call of its own
+    // (measured on C3, 1,000 masks x 10,000 queries at allowed fraction 0.5: 567 ms grouped,
+    // 423 ms as 1,000 calls; the rows are the same either way).
+    g.own = !g.width && !forced && multi_form_env() != 1 && overfetch_kp(ix, g.m, k, (int64_t)g.qi.size()) > 0;
+    if (g.own) continue;
+    if (!g.width) {
+      g.scan = g.qi;
+      st[3] += (int64_t)g.qi.size();
+    }
+    n_scan_max += (int64_t)g.qi.size();   // every query may end in the gathered scan
+    ++n_groups_scan;
+  }
+  const bool loop = multi_loop_form(ix, gs);
+  if (loop) st[3] = 0;   // counted per sub-call
+  int64_t acc[2] = {0, 0};
+  if ((rc = multi_own_calls(ix, gs, loop, q, nq, k, ids, scores, acc, up, s))) return rc;
+  ix->mask_stats[0] = 4;   // the sub-calls wrote their own
+  ix->mask_stats[1] = acc[0];
+  ix->mask_stats[2] = acc[1];
+  ix->mask_stats[3] = live;
+  if (loop)   // no shared widths, no grouped launches: [1], [4] and [5] stay 0
+    for (MultiGroup& g : gs) g.width = 0, g.scan.clear();
+  for (MultiGroup& g : gs) {
+    if (!g.width) continue;
+    // a small call's unmasked filter grows smoothly with k' (the comment at kMaskMaxKp): one
+    // call at the widest k' of its masks, unrounded, costs less than one per width
+    if (nq <= kMaskSmallQ) g.width = widths[3] = w_max, widths[0] = widths[1] = widths[2] = 0;
+    for (int i = 0; i < 4; ++i)
+      if (widths[i] == g.width) {
+        n_w[i] += (int64_t)g.qi.size();
+        break;
+      }
+  }
+  // the over-fetch queries width by width: their positions in the call (gather and result row)
+  // and their mask slots
+  std::vector<int64_t> src;
+  std::vector<int> qs, qo;
+  for (int i = 0; i < 4; ++i) {
+    if (!n_w[i]) continue;
+    for (size_t g = 0; g < gs.size(); ++g) {
+      if (gs[g].width != widths[i]) continue;
+      for (int o : gs[g].qi) {
+        src.push_back(o);
+        qs.push_back((int)g);
+        qo.push_back(o);
+      }
+    }
+    n_ov += n_w[i];
+    n_ovw = std::max(n_ovw, n_w[i] * widths[i]);
+    st[1] += 1;
+    ix->mask_stats[1] = std::max<int64_t>(ix->mask_stats[1], widths[i]);
+  }
+  st[0] += n_ov;
+  std::vector<MaskSlot> slots(n_ov ? gs.size() : 0);
+  for (size_t g = 0; g < slots.size(); ++g) slots[g] = MaskSlot{gs[g].m->bits, gs[g].m->n_allowed};
+  const size_t o_src = tb.add(src), o_qs = tb.add(qs), o_qo = tb.add(qo), o_sl = tb.add(slots);
+  // ---- the handle's mk buffer: tables, flags, the unmasked results, the gathered queries ----
+  const int64_t max_slots = n_scan_max + (int64_t)(kMpXQ - 1) * n_groups_scan;
+  const int64_t n_stage = std::max<int64_t>(1, std::max(n_ov, max_slots));
+  const size_t o_fl = round_up((int64_t)tb.h.size() + 1, 256), o_tid = o_fl + round_up(nq * 4, 256),
+               o_ts = o_tid + round_up(n_ovw * 8 + 8, 256), o_tq = o_ts + round_up(n_ovw * 4 + 4, 256),
+               tot = o_tq + round_up(n_stage * D * 4, 256);
+  if ((rc = ix->mk.reserve(tot, ix->busy()))) return rc;
+  char* mk = ix->mk.as<char>();
+  int* flag = (int*)(mk + o_fl);
+  int64_t* tid = (int64_t*)(mk + o_tid);
+  float* ts = (float*)(mk + o_ts);
+  float* tq = (float*)(mk + o_tq);
+  HIPCHK(up.send(tb, mk));
+  HIPCHK(launch_mask_fill_rows(ids, scores, k, (const int*)(mk + o_fill), (int)fill.size(), s));
+  // ---- over-fetch: one unmasked call per width over the queries of all its masks ----
+  if (n_ov > 0) {
+    HIPCHK(hipMemsetAsync(flag, 0, (size_t)nq * 4, s));
+    HIPCHK(launch_copy_rows(q, D, (const int64_t*)(mk + o_src), tq, D, nullptr, n_ov, D, s));
+    int64_t q0 = 0;
+    for (int i = 0; i < 4; ++i) {
+      if (!n_w[i]) continue;
+      const int W = widths[i];
+      const int64_t n = n_w[i];
+      scan_cfg_begin(n);   // the sub-call's own scan configuration
+      rc = score_topk_unmasked(ix, tq + q0 * D, n, W, tid, ts, s);
+      scan_cfg_begin(nq);
+      if (rc) return rc;
+      HIPCHK(launch_mask_overfetch_multi(tid, ts, (int)n, W, k, (const MaskSlot*)(mk + o_sl), (const int*)(mk + o_qs) + q0,
+                                         (const int*)(mk + o_qo) + q0, ids, scores, flag, s));
+      q0 += n;
+    }
+    // the short flags of every width, read back once
+    if ((rc = ix->hflags.reserve((size_t)nq * sizeof(int)))) return rc;
+    HIPCHK(hipMemcpyAsync(ix->hflags.p, flag, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int* hflag = ix->hflags.as<int>();
+    int64_t n_short = 0;
+    for (MultiGroup& g : gs) {
+      if (!g.width) continue;
+      for (int o : g.qi)
+        if (hflag[o]) g.scan.push_back(o);
+      n_short += (int64_t)g.scan.size();
+    }
+    st[0] -= n_short;   // answered by the over-fetch leg: not the short ones
+    st[2] += n_short;
+    ix->mask_stats[2] = st[2];
+  }
+  // ---- the gathered scan, grouped ----
+  if ((rc = multi_gathered(ix, gs, q, k, ids, scores, tq, n_stage, up, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));   // the uploads' host tables go with this frame
+  ix->ws_idle = true;
+  return CWQ_OK;
+}
+
+}  // namespace
+
+extern "C" int cwq_score_topk_masked_multi(cwq_index* ix, const cwq_mask* const* masks, int32_t n_masks,
+                                           const int32_t* mask_of_query, const float* q, int64_t nq, int32_t k,
+                                           int64_t* ids, float* scores, void* stream) {
+  if (!ix || !masks || !mask_of_query || (!q && nq > 0) || (!ids && nq > 0)) return fail(CWQ_ERR_ARG, "NULL argument");
+  if (n_masks < 1) return fail(CWQ_ERR_ARG, "n_masks must be >= 1");
+  if (k <= 0) return fail(CWQ_ERR_ARG, "k must be >= 1");
+  if (nq < 0 || nq > INT_MAX) return fail(CWQ_ERR_ARG, "nq must be in [0, 2^31)");
+  for (int32_t i = 0; i < n_masks; ++i) {
+    if (!masks[i]) return fail(CWQ_ERR_ARG, "masks[" + std::to_string(i) + "] is NULL");
+    if (!mask_of_index(ix, masks[i])) return fail(CWQ_ERR_ARG, "the mask was built for another index");
+  }
+  for (int64_t i = 0; i < nq; ++i)
+    if (mask_of_query[i] < 0 || mask_of_query[i] >= n_masks)
+      return fail(CWQ_ERR_ARG, "mask_of_query[" + std::to_string(i) + "] = " + std::to_string(mask_of_query[i]) +
+                                   " is outside [0, " + std::to_string(n_masks) + ")");
+  if (nq == 0) return CWQ_OK;
+  // counting sort by distinct mask (a mask named by two slots is one group)
+  std::vector<int> group_of_slot((size_t)n_masks, -1);
+  std::vector<MultiGroup> gs;
+  {
+    std::map<const cwq_mask*, int> seen;
+    std::vector<char> used((size_t)n_masks, 0);
+    for (int64_t i = 0; i < nq; ++i) used[mask_of_query[i]] = 1;
+    for (int32_t i = 0; i < n_masks; ++i) {
+      if (!used[i]) continue;
+      auto it = seen.find(masks[i]);
+      if (it == seen.end()) {
+        it = seen.emplace(masks[i], (int)gs.size()).first;
+        gs.push_back(MultiGroup());
+        gs.back().m = masks[i];
+      }
+      group_of_slot[i] = it->second;
+    }
+    for (int64_t i = 0; i < nq; ++i) gs[group_of_slot[mask_of_query[i]]].qi.push_back((int)i);
+  }
+  if (gs.size() == 1) {   // one mask for every query: the single-mask call, its path and its stats
+    {
+      std::lock_guard<std::mutex> lk(ix->mu);
+      for (int64_t& t : ix->mask_multi_stats) t = 0;
+      ix->mask_multi_stats[6] = 1;
+    }
+    return cwq_score_topk_masked(ix, gs[0].m, q, nq, k, ids, scores, stream);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  QueryCall call(ix, nq, s);
+  topk_begin(ix);
+  for (int64_t& t : ix->mask_stats) t = 0;
+  for (int64_t& t : ix->mask_multi_stats) t = 0;
+  ix->mask_multi_stats[6] = (int64_t)gs.size();
+  if (call.rc) return call.rc;
+  return masked_multi_impl(ix, gs, q, nq, k, ids, scores, s);
+}
+
+extern "C" int cwq_last_mask_multi_stats(const cwq_index* ix, int64_t* out) {
+  if (!ix || !out) return fail(CWQ_ERR_ARG, "NULL argument");
+  for (int i = 0; i < 8; ++i) out[i] = ix->mask_multi_stats[i];
   return CWQ_OK;
 }

@@ -359,14 +359,36 @@ class CobwebIndex:
         check(self._L.cwq_last_mask_stats(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         return {"path": int(out[0]), "overfetch_k": int(out[1]), "redone_queries": int(out[2]), "live_rows": int(out[3])}
 
-    def score_topk(self, q, k, mask=None):
+    def last_mask_multi_stats(self):
+        """The last score_topk(masks=...) call over more than one distinct mask
+        (cwq_last_mask_multi_stats): queries answered by the over-fetch leg, distinct over-fetch
+        widths run, queries the over-fetch left short, queries planned straight to the gathered
+        scan, gathered-scan kernel launches and work items, distinct masks referenced, queries
+        through the k > 64 sort.  A mask that ran as a single-mask call of its own inside the call
+         counts its queries by what that call did; the launches and work items are
+        the grouped scan's only."""
+        out = np.zeros(8, np.int64)
+        check(self._L.cwq_last_mask_multi_stats(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        names = ["overfetch_queries", "overfetch_widths", "short_queries", "gathered_queries", "gathered_launches",
+                 "gathered_work_items", "masks_referenced", "sort_queries"]
+        return dict(zip(names, (int(v) for v in out)))
+
+    def score_topk(self, q, k, mask=None, masks=None, mask_of_query=None):
         """Top-k sentence ids/scores per query ("Cobweb Fast", A6).  One call per query is
         the reference harness's mode (benchmark_utils.py:801-805), so a float32 [nq, dim]
         tensor already on the index device goes straight through: no conversion, no device
         switch (the library selects its device itself), the raw current stream.
         mask (a SentenceMask of this index): the ranking restricted to its allowed sentences --
         the full ranking with the others removed, cut to k, padded with -1 / -inf
-        (cwq_score_topk_masked)."""
+        (cwq_score_topk_masked).
+        masks (a sequence of open SentenceMasks of this index) with mask_of_query (an int tensor /
+        array / list of length nq; a device tensor is copied to the host once): query i is
+        restricted to masks[mask_of_query[i]], in one call (cwq_score_topk_masked_multi; each row
+        is what the single-mask call returns for it).  Not together with mask=."""
+        if masks is not None and mask is not None:
+            raise ValueError("pass mask= or masks=, not both")
+        if (masks is None) != (mask_of_query is None):
+            raise ValueError("masks= and mask_of_query= go together")
         if not (type(q) is torch.Tensor and q.dtype == torch.float32 and q.device == self.device and q.dim() == 2
                 and q.shape[1] == self.dim and q.is_contiguous()):
             q = self._queries(q)
@@ -374,6 +396,19 @@ class CobwebIndex:
         k = int(k)
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        if masks is not None:
+            masks = list(masks)
+            if not masks or any(not isinstance(m, SentenceMask) or m.closed for m in masks):
+                raise ValueError("masks must be a non-empty sequence of open SentenceMasks (CobwebIndex.sentence_mask)")
+            moq = mask_of_query.detach().cpu().numpy() if torch.is_tensor(mask_of_query) else np.asarray(mask_of_query)
+            if moq.ndim != 1 or moq.shape[0] != nq or moq.dtype.kind not in "iu":
+                raise ValueError(f"mask_of_query must be {nq} integers, one per query")
+            moq = np.ascontiguousarray(moq.clip(-1, 2 ** 31 - 1), dtype=np.int32)   # out of range stays out of range
+            handles = (ctypes.c_void_p * len(masks))(*[m._h.value for m in masks])
+            check(self._L.cwq_score_topk_masked_multi(self._h, handles, len(masks), moq.ctypes.data, q.data_ptr(), nq, k,
+                                                      ids.data_ptr(), scores.data_ptr(),
+                                                      _stream_raw(self.device.index)))
+            return ids, scores
         if mask is not None:
             if not isinstance(mask, SentenceMask) or mask.closed:
                 raise ValueError("mask must be an open SentenceMask (CobwebIndex.sentence_mask)")

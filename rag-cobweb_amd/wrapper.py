@@ -418,11 +418,64 @@ class CobwebWrapper:
         return results
 
     # batched extensions (the benchmark's unit of work)
-    def cobweb_predict_batch(self, queries, k=5, allowed=None):
+    def sentence_masks_by_label(self, label_of_sentence):
+        """One SentenceMask per distinct label (tenant, ACL group, date bucket, ...) of an integer
+        label per sentence -> (masks, values), `values` the distinct labels sorted and masks[j]
+        the sentences labelled values[j].  For a batch whose query i may see label
+        label_of_query[i] only:
+
+            masks, values = w.sentence_masks_by_label(label_of_sentence)
+            set_of_query = torch.searchsorted(values, label_of_query)   # every query label must be in values
+            ids, scores = w.cobweb_predict_batch(Q, k, allowed_sets=masks, set_of_query=set_of_query)
+
+        A mask takes 1 B per leaf-class row + 4 B per live row + 1 bit per sentence of device
+        memory, whatever its size: 1,000 masks over 1M sentences are about 1.1 GB.
+        The masks belong to the current prediction index, like sentence_mask's; close them when
+        done."""
+        self.build_prediction_index()
+        lab = torch.as_tensor(label_of_sentence).reshape(-1)
+        if lab.dtype.is_floating_point or lab.dtype.is_complex or lab.dtype == torch.bool:
+            raise ValueError("label_of_sentence must be integers")
+        if lab.numel() != self._index.n_sent:
+            raise ValueError(f"label_of_sentence must have one entry per sentence: got {lab.numel()}, the index has "
+                             f"{self._index.n_sent}")
+        # one sort of the labels, then each mask from its own run of sentence ids: the work
+        # is O(n log n) in all, not one pass over the sentences per label
+        values, counts = torch.unique(lab, sorted=True, return_counts=True)
+        runs = torch.split(torch.argsort(lab, stable=True), counts.tolist())
+        masks = []
+        try:
+            for ids in runs:
+                masks.append(self._index.sentence_mask(ids))
+        except Exception:
+            for m in masks:   # a failed build leaks no mask
+                m.close()
+            raise
+        return masks, values
+
+    def cobweb_predict_batch(self, queries, k=5, allowed=None, allowed_sets=None, set_of_query=None):
         """[Q, D] queries -> (ids [Q, k] int64 tensor, scores [Q, k] float32), Fast path.
         allowed: as in cobweb_predict_indexed, one set for the whole block (-1 / -inf past the
-        allowed sentences)."""
+        allowed sentences).
+        allowed_sets with set_of_query (no reference counterpart): a sequence of sets -- each a
+        SentenceMask, a bool mask or sentence ids -- and one index into it per query; query i
+        is ranked over allowed_sets[set_of_query[i]] only, in one call.  (A keyword of its own:
+        allowed=[1, 2, 3] already means sentence ids.)  Not together with allowed=."""
+        if allowed_sets is not None and allowed is not None:
+            raise ValueError("pass allowed= or allowed_sets=, not both")
+        if (allowed_sets is None) != (set_of_query is None):
+            raise ValueError("allowed_sets= and set_of_query= go together")
         self.build_prediction_index()
+        if allowed_sets is not None:
+            made = []
+            try:
+                for a in allowed_sets:
+                    made.append(self._mask_for(a))
+                return self._index.score_topk(queries, k, masks=[m for m, _ in made], mask_of_query=set_of_query)
+            finally:
+                for m, mine in made:
+                    if mine:
+                        m.close()
         if allowed is None:
             return self._index.score_topk(queries, k)
         mask, mine = self._mask_for(allowed)

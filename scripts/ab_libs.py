@@ -18,6 +18,12 @@ every repetition) and checks that the arms return the same bits.
 
     python scripts/ab_libs.py --libs a.so,b.so --clusters 100 --categorize 1,64,1024
 
+    python scripts/ab_libs.py --libs parent.so,new.so --masked 1,16,10000 --fractions 1,0.5,0.1,0.01
+
+--masked times the single-mask call score_topk(Q, k, mask=) per query count and allowed fraction
+(scripts/mask_probe.py's cells; each arm builds its own mask from the same flags; HIP events,
+the arms taking turns inside every repetition) and checks that the arms return the same bits.
+
 --categorize times Basic (categorize) on the list paths (CWQ_CAT_DIRECT=0): host wall time of
 the call plus a device synchronize (time.perf_counter, not HIP events), the arms taking turns
 inside every repetition, and checks that the arms return the same nodes, found counts and call
@@ -77,6 +83,36 @@ def rank_ce_ab(paths, arms, Q, nqs, reps):
                   f"{'same bits' if same else 'MISMATCH'}", flush=True)
 
 
+def masked_ab(paths, arms, Q, nqs, fractions, reps, k):
+    gen = torch.Generator(device=Q.device).manual_seed(7)
+    n = arms[0].n_sent
+    for f in fractions:
+        flags = torch.rand(n, device=Q.device, generator=gen) < f if f < 1 else torch.ones(n, dtype=torch.bool, device=Q.device)
+        masks = [ix.sentence_mask(flags) for ix in arms]
+        for nq in nqs:
+            q = Q[:nq].contiguous()
+            outs = [ix.score_topk(q, k, mask=m) for ix, m in zip(arms, masks)]
+            same = all(torch.equal(a, b) for o in outs[1:] for a, b in zip(o, outs[0]))
+            path = [ix.last_mask_stats()["path"] for ix in arms]
+            torch.cuda.synchronize()
+            ts = [[] for _ in arms]
+            for _ in range(reps):
+                for i, (ix, m) in enumerate(zip(arms, masks)):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    ix.score_topk(q, k, mask=m)
+                    b.record()
+                    b.synchronize()
+                    ts[i].append(a.elapsed_time(b))
+            med = [statistics.median(t) for t in ts]
+            for p, t, m, pa in zip(paths, ts, med, path):
+                print(f"masked f={f:g} nq={nq} {os.path.basename(p)[:60]}: {m:.3f} ms [{min(t):.3f}, {max(t):.3f}]  "
+                      f"x{m / med[0]:.4f} vs first, own spread {(max(t) - min(t)) / m:.1%}  path {pa}  "
+                      f"{'same bits' if same else 'MISMATCH'}", flush=True)
+        for m in masks:
+            m.close()
+
+
 def categorize_ab(paths, arms, Q, nqs, reps, k):
     """Basic (categorize) per arm, the arms taking turns inside every repetition (host wall time
     of the call plus a synchronize); nodes, found and calls must be equal between the arms.  CWQ_CAT_DIRECT=0 as in the tests: the path choice is
@@ -112,6 +148,8 @@ def main():
                     help="one index for every arm (same library; knobs read per call only)")
     ap.add_argument("--rank-ce", default="", help="query counts: time rank_ce (loss + grad_q) per arm instead")
     ap.add_argument("--categorize", default="", help="query counts: time categorize per arm instead")
+    ap.add_argument("--masked", default="", help="query counts: time the single-mask score_topk(mask=) per arm instead")
+    ap.add_argument("--fractions", default="1,0.5,0.1,0.01", help="--masked: allowed fractions")
     ap.add_argument("--reps", type=int, default=9, help="--rank-ce / --categorize: repetitions")
     ap.add_argument("--clusters", type=int, default=0, help="0: flat tree; G: root -> G random clusters -> leaves")
     args = ap.parse_args()
@@ -149,6 +187,10 @@ def main():
     torch.cuda.empty_cache()
     if args.rank_ce:
         rank_ce_ab(paths, arms, Q, [int(v) for v in args.rank_ce.split(",")], args.reps)
+        return
+    if args.masked:
+        masked_ab(paths, arms, Q, [int(v) for v in args.masked.split(",")], [float(v) for v in args.fractions.split(",")],
+                  args.reps, args.k)
         return
     if args.categorize:
         categorize_ab(paths, arms, Q, [int(v) for v in args.categorize.split(",")], args.reps, args.k)
