@@ -228,6 +228,56 @@ int cwq_rank_ce_w(cwq_index* idx, const float* q, int64_t nq, const int64_t* tar
                   int64_t* rank, void* stream);
 
 /*
+ * Sparse differentiable scores (no reference counterpart: the reference scores every leaf,
+ * CobwebWrapper.py:267-294): the Fast scores of a short list of sentences per
+ * query, their backward, and the cross-entropy loss over the exact top-K plus the target.
+ * All three validate their arguments before any device work (CWQ_ERR_ARG for a NULL required
+ * pointer, nq < 0, m < 1, K < 1 or a temperature that is not finite and > 0), treat nq == 0 as
+ * a no-op, run on `stream`, use no float atomics (every output is bit-identical from run to
+ * run, and a query's outputs are the same alone, in any batch and under any workspace
+ * chunking) and keep no state between calls.
+ *
+ * cwq_score_pairs
+ *   ids     device [nq*m] int64: m sentence ids per query; duplicates allowed; any m >= 1
+ *   scores  device [nq*m]: scores[q][j] = the Fast score of sentence ids[q][j] for query q, bit
+ *           for bit the value cwq_rank_scores writes in that column; -inf for an id of -1, an
+ *           id outside [0, n_sent) and a sentence that is in no node
+ *
+ * cwq_score_pairs_backward
+ *   grad_scores  device [nq*m]: the upstream gradient of every score.  Entries whose score is
+ *                -inf are never read (cwq_rank_scores_backward's rule); duplicates add
+ *   grad_q       device [nq*dim]: d(sum_j grad_scores[q][j] * score(q, ids[q][j])) / dq
+ *   Needs nothing from a forward call.  m <= 4096; above it CWQ_ERR_ARG (scatter the gradient
+ *   into [nq*n_sent] and call cwq_rank_scores_backward).
+ *
+ * cwq_rank_ce_topk
+ *   The candidate set C of a query is what cwq_score_topk(K) returns for it (its order, its tie
+ *   rule, its scores) plus the target when it is not among them.  With T the temperature, m the
+ *   largest candidate score, z = sum_C exp((s - m)/T) and s_K the lowest top-K score:
+ *   loss         device [nq]: (m - s_target)/T + log z
+ *   grad_q       device [nq*dim] or NULL (forward only): d loss / dq, through the sparse backward
+ *                with g_j = (exp((s_j - m)/T)/z - [j = target]) / T; needs K + 1 <= 4096
+ *   target_score device [nq] or NULL: the bits cwq_rank_scores gives
+ *   rank         device [nq] int64 or NULL: the exact 1-based rank (cwq_rank_ce's) when the target
+ *                is inside the top-K, otherwise K + 1 = "at least K + 1"
+ *   tail_bound   device [nq] or NULL: a certified upper bound of cwq_rank_ce's loss minus this
+ *                loss, log1p((n_tree - |C|) exp((s_K - m)/T) / z) with n_tree the sentences that
+ *                are in the tree (every sentence outside C scores at most s_K); 0 when fewer
+ *                than K sentences exist
+ *   cand_ids     device [nq*K] int64 or NULL: the row cwq_score_topk returns
+ *   A target outside [0, n_sent) or whose sentence is not in the tree: loss +inf, a zero grad_q
+ *   row, target_score -inf, rank -1, tail_bound 0 (cwq_rank_ce's result); the other queries are
+ *   not disturbed.  Any K >= 1 that cwq_score_topk accepts; K <= 64 is the hot form.
+ */
+int cwq_score_pairs(cwq_index* idx, const float* q, int64_t nq, const int64_t* ids, int32_t m, float* scores,
+                    void* stream);
+int cwq_score_pairs_backward(cwq_index* idx, const float* q, int64_t nq, const int64_t* ids, int32_t m,
+                             const float* grad_scores, float* grad_q, void* stream);
+int cwq_rank_ce_topk(cwq_index* idx, const float* q, int64_t nq, const int64_t* target, float temperature, int32_t K,
+                     float* loss, float* grad_q, float* target_score, int64_t* rank, float* tail_bound,
+                     int64_t* cand_ids, void* stream);
+
+/*
  * Per-node Gaussian log-likelihood for every node in BFS order.
  *   full = 0: lp'(n) as CobwebWrapper.py:232-236 (no 2*pi term)
  *   full = 1: CobwebTorchNode.log_prob (CobwebTorchNode.py:100-104, with 2*pi)

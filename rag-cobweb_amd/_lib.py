@@ -41,6 +41,9 @@ SIGNATURES = {
     "cwq_rank_scores_w": (_c.c_int, [_P, _P, _I64, _P, _c.c_int32, _P, _P]),
     "cwq_rank_scores_backward_w": (_c.c_int, [_P, _P, _I64, _P, _P, _c.c_int32, _P, _P, _P]),
     "cwq_rank_ce_w": (_c.c_int, [_P, _P, _I64, _P, _c.c_float, _P, _c.c_int32, _P, _P, _P, _P, _P, _P]),
+    "cwq_score_pairs": (_c.c_int, [_P, _P, _I64, _P, _I32, _P, _P]),
+    "cwq_score_pairs_backward": (_c.c_int, [_P, _P, _I64, _P, _I32, _P, _P, _P]),
+    "cwq_rank_ce_topk": (_c.c_int, [_P, _P, _I64, _P, _c.c_float, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "cwq_node_logprob": (_c.c_int, [_P, _P, _I64, _I32, _P, _P]),
     "cwq_prefix_bounds": (_c.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
     "cwq_categorize": (_c.c_int, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P]),

@@ -123,3 +123,94 @@ def rank_scores_autograd(index, q, level_weights=None):
     q = q.to(index.device, torch.float32).contiguous()
     w = _weights(index, level_weights)
     return RankScores.apply(q, index, w)
+
+
+class TopKScores(torch.autograd.Function):
+    """(ids, scores) = index.score_topk(q, k, ...) with the scores differentiable in q (DESIGN.md
+    §4.18): the backward is cwq_score_pairs_backward over the returned ids, whose padded (-1 /
+    -inf) entries contribute nothing.  Plain, mask= and masks= calls alike."""
+
+    @staticmethod
+    def forward(ctx, q, index, k, mask, masks, mask_of_query):
+        ctx.index = index
+        ctx.pin = _Pin(index)
+        ids, scores = index.score_topk(q.detach(), k, mask=mask, masks=masks, mask_of_query=mask_of_query)
+        ctx.save_for_backward(q, ids)
+        ctx.mark_non_differentiable(ids)
+        return ids, scores
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _gi, grad_scores):
+        q, ids = ctx.saved_tensors
+        return ctx.index.score_pairs_backward(q, ids, grad_scores), None, None, None, None, None
+
+
+class PairScores(torch.autograd.Function):
+    """scores = index.score_pairs(q, ids); backward cwq_score_pairs_backward."""
+
+    @staticmethod
+    def forward(ctx, q, index, ids):
+        ctx.index = index
+        ctx.pin = _Pin(index)
+        ctx.save_for_backward(q, ids)
+        return index.score_pairs(q.detach(), ids)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_scores):
+        q, ids = ctx.saved_tensors
+        return ctx.index.score_pairs_backward(q, ids, grad_scores), None, None
+
+
+class RankCETopK(torch.autograd.Function):
+    """(loss, target_score, rank, tail_bound, cand_ids) = index.rank_ce_topk(q, target, K, T).
+    Like RankCE the forward computes d loss / d q where it is needed and saves it, so the
+    backward is torch arithmetic; the index is pinned all the same, as RankScores pins it."""
+
+    @staticmethod
+    def forward(ctx, q, index, target, K, temperature, need):
+        ctx.pin = _Pin(index)
+        loss, gq, tscore, rank, bound, cand = index.rank_ce_topk(q.detach(), target, K, temperature, grad=need)
+        ctx.need = need
+        ctx.save_for_backward(*([gq] if need else []))
+        ctx.mark_non_differentiable(tscore, rank, bound, cand)
+        return loss, tscore, rank, bound, cand
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, *_):
+        gq = ctx.saved_tensors[0] * grad_loss[:, None] if ctx.need else None
+        return gq, None, None, None, None, None
+
+
+def _queries_autograd(index, q):
+    """The move to the index device, the cast and the [dim] -> [1, dim] reshape as torch ops: a
+    CPU leaf gets its gradient on the CPU."""
+    q = torch.as_tensor(q)
+    if q.dim() == 1:
+        q = q[None, :]
+    if q.dim() != 2 or q.shape[1] != index.dim:
+        raise ValueError(f"queries must be [nq, {index.dim}]")
+    return q.to(index.device, torch.float32).contiguous()
+
+
+def topk_scores_autograd(index, q, k, mask=None, masks=None, mask_of_query=None):
+    if int(k) > 4096:   # cwq_score_pairs_backward's entry limit: fail here, not in a later backward()
+        raise ValueError("score_topk with a query that requires grad takes k <= 4096 (the sparse backward's limit): "
+                         "detach the query, or differentiate rank_scores")
+    return TopKScores.apply(_queries_autograd(index, q), index, int(k), mask, masks, mask_of_query)
+
+
+def pair_scores_autograd(index, q, ids):
+    q = _queries_autograd(index, q)
+    return PairScores.apply(q, index, index._pair_ids(ids, q.shape[0]))
+
+
+def rank_ce_topk_autograd(index, q, target, K, temperature=1.0):
+    """Differentiable per-query loss of index.rank_ce_topk with the target's score, its rank, the
+    tail bound and the candidate ids (all non-differentiable).  Under torch.no_grad(), or for a
+    q that does not require grad, no gradient pass runs."""
+    q = _queries_autograd(index, q)
+    need = bool(q.requires_grad and torch.is_grad_enabled())
+    return RankCETopK.apply(q, index, target, int(K), float(temperature), need)

@@ -1,6 +1,7 @@
 // The query library's host layer behind the C ABI: the handle (struct cwq_index), the per-call
 // scopes, the query chunk, and the declarations of the host functions that cross a file.
-// Host only: included by cwq_api.hip, cwq_rank.hip, cwq_fitcalls.hip and cwq_maskcalls.hip and by nothing else; the
+// Host only: included by cwq_api.hip, cwq_rank.hip, cwq_fitcalls.hip, cwq_maskcalls.hip and cwq_sparsecalls.hip and by
+// nothing else; the
 // kernel sources share cwq_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -964,6 +964,48 @@ hipError_t launch_ce_reduce(const CeArgs& a, hipStream_t s);
 // ce_coef_kernel: coefL / hL [qtiles][NL][16] of the loss's gradient (grad_rows_kernel's layout)
 hipError_t launch_ce_coef(const CeArgs& a, const RowMeta* meta, int NL_iso, float* coefL, float* hL, hipStream_t s);
 
+// ---- sparse differentiable scores (cwq_sparse.hip) ----
+constexpr int kSparseMaxM = 4096;        // entries per query of the sparse backward (its LDS lists)
+constexpr int kSparseLdsBytes = 65536 - 64;   // dynamic LDS of sparse_grad_kernel: 12 m B of lists, + 4 NI B when a query's c[p] fits beside them
+// out[q][j] = the exact Fast key of sentence ids[q][j]'s row (-inf: no such row), the scan's bits
+struct SparsePairArgs {
+  const float* X; int DP; int nq, m;     // the chunk's padded queries (pad_queries layout)
+  const int64_t* ids; int64_t ld_ids;
+  int64_t n_sent; const int* row_of_sent;
+  int NL_iso;
+  const float* Mf;                       // isotropic rows, row-major [row][DP]
+  const float* anA; const float* anB; int64_t ld_an;
+  const RowMeta* meta; const int* par;   // of all leaf-class rows
+  const float* P; int64_t ldP;           // [nq_pad][ldP] exact prefixes (query-major)
+  float dconst;
+  float* out; int64_t ld_out;
+};
+hipError_t launch_sparse_pairs(const SparsePairArgs& a, hipStream_t s);
+// grad of sum_j g[q][j] score(q, ids[q][j]): the leaf-class rows' term into part[0][q][DP] (slab
+// 0 of grad_reduce's layout) and the internal nodes' coefficients coefI [qtiles][NI][16] for
+// launch_grad_stream
+struct SparseGradArgs {
+  const float* q; int nq, qtiles, D, DP, m;
+  const int64_t* ids; const float* g;    // [nq][m]
+  int64_t n_sent; const int* row_of_sent;
+  int NL_iso, NI;
+  const float* Mf; const float* anA; const float* anB; int64_t ld_an;
+  const RowMeta* meta; const int* par; const int* par_int; const float* w_int;
+  float* part; float* cI; float* coefI;
+  int c_lds;                             // set by the launcher
+};
+hipError_t launch_sparse_grad(SparseGradArgs a, hipStream_t s);
+// the truncated loss over the top-K list and the target (one wave per query)
+struct SparseCeArgs {
+  int nq, K, NL; float invT;
+  const int64_t* top_ids; const float* top_scores;   // [nq][K], cwq_score_topk's
+  const int64_t* target; const float* tscore;        // [nq]; tscore: the target's key (pair kernel)
+  int64_t n_sent; const int* row_of_sent; const int64_t* sent_ptr;
+  float* loss; float* tscore_out; int64_t* rank; float* tail_bound; int64_t* cand_ids;
+  int64_t* bid; float* bg;                           // [nq][K + 1] the backward's list, or null
+};
+hipError_t launch_ce_topk(const SparseCeArgs& a, hipStream_t s);
+
 // ---- call-time level weights and their gradient (cwq_lweight.hip) ----
 constexpr int kLwPart = 256;        // rows (nodes) per fp64 partial line: a function of the index alone
 constexpr int kLwMaxLevels = 64;    // level weights a call may pass

@@ -384,7 +384,15 @@ class CobwebIndex:
         masks (a sequence of open SentenceMasks of this index) with mask_of_query (an int tensor /
         array / list of length nq; a device tensor is copied to the host once): query i is
         restricted to masks[mask_of_query[i]], in one call (cwq_score_topk_masked_multi; each row
-        is what the single-mask call returns for it).  Not together with mask=."""
+        is what the single-mask call returns for it).  Not together with mask=.
+        A q that requires grad (with grad enabled) gets scores with autograd history, as
+        torch.topk's values have and its indices do not (autograd.TopKScores; the backward is
+        cwq_score_pairs_backward over the returned ids); k <= 4096 then, ValueError
+        above.  Without grad the call is the one described above."""
+        if getattr(q, "requires_grad", False) and torch.is_grad_enabled():
+            # values carry the gradient, indices do not (torch.topk); the backward needs only the ids
+            from .autograd import topk_scores_autograd
+            return topk_scores_autograd(self, q, k, mask, masks, mask_of_query)
         if masks is not None and mask is not None:
             raise ValueError("pass mask= or masks=, not both")
         if (masks is None) != (mask_of_query is None):
@@ -561,6 +569,89 @@ class CobwebIndex:
                                             _ptr(gw) if weight_grad and n_w else None, _ptr(tscore), _ptr(rank),
                                             _stream(self.device)))
         return (loss, gq, tscore, rank, gw) if weight_grad else (loss, gq, tscore, rank)
+
+    def _pair_ids(self, ids, nq):
+        t = torch.as_tensor(ids)
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError("ids must hold integer sentence ids")
+        if t.dim() == 1:
+            t = t[None, :] if nq == 1 else t[:, None]
+        if t.dim() != 2 or t.shape[0] != nq or t.shape[1] < 1:
+            raise ValueError(f"ids must be [{nq}, m] with m >= 1")
+        return t.to(self.device, torch.int64).contiguous()
+
+    def score_pairs(self, q, ids):
+        """The Fast scores of given sentences (cwq_score_pairs): q [nq, dim], ids
+        [nq, m] sentence ids per query -> [nq, m] float32, each the bits rank_scores has in that
+        column; -inf for an id of -1, an id outside [0, n_sent) and a sentence outside the tree.
+        No [nq, n_sent] tensor is made.  A q that requires grad (with grad enabled) gets scores
+        with autograd history (autograd.PairScores)."""
+        if getattr(q, "requires_grad", False) and torch.is_grad_enabled():
+            from .autograd import pair_scores_autograd
+            return pair_scores_autograd(self, q, ids)
+        q = self._queries(q)
+        nq = q.shape[0]
+        ids = self._pair_ids(ids, nq)
+        out = torch.empty(ids.shape, dtype=torch.float32, device=self.device)
+        if nq > 0:
+            with torch.cuda.device(self.device):
+                check(self._L.cwq_score_pairs(self._h, _ptr(q), nq, _ptr(ids), ids.shape[1], _ptr(out),
+                                              _stream(self.device)))
+        return out
+
+    def score_pairs_backward(self, q, ids, grad):
+        """Gradient of score_pairs with respect to the queries (cwq_score_pairs_backward): grad
+        [nq, m], the upstream gradient of every score (entries whose score is -inf are never
+        read; duplicates add) -> [nq, dim] float32.  m <= 4096.  Needs nothing from the forward
+        call; bit-identical from run to run and for a query alone or in a batch."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        ids = self._pair_ids(ids, nq)
+        g = torch.as_tensor(grad, dtype=torch.float32)
+        if g.dim() == 1:
+            g = g.reshape(ids.shape) if g.numel() == ids.numel() else g
+        if g.shape != ids.shape:
+            raise ValueError(f"grad must be {list(ids.shape)}")
+        g = g.to(self.device).contiguous()
+        out = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device)
+        if nq > 0:
+            with torch.cuda.device(self.device):
+                check(self._L.cwq_score_pairs_backward(self._h, _ptr(q), nq, _ptr(ids), ids.shape[1], _ptr(g),
+                                                       _ptr(out), _stream(self.device)))
+        return out
+
+    def rank_ce_topk(self, q, target, K, temperature=1.0, grad=False):
+        """Cross-entropy loss over the exact top-K plus the target (cwq_rank_ce_topk, DESIGN
+        §4.18): -> (loss [nq], grad_q [nq, dim] or None when grad is False, target_score [nq],
+        rank [nq] int64: exact inside the top-K, else K + 1, tail_bound [nq]: an upper bound of
+        rank_ce's loss minus this loss, cand_ids [nq, K]: score_topk's row).  A target outside
+        the tree: loss inf, a zero gradient row, score -inf, rank -1, bound 0."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        t = torch.as_tensor(target)
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError("target must hold integer sentence ids")
+        t = t.reshape(-1).to(self.device, torch.int64).contiguous()
+        if t.shape[0] != nq:
+            raise ValueError(f"target must be [{nq}]")
+        K = int(K)
+        if K < 1:
+            raise ValueError("K must be >= 1")
+        temperature = float(temperature)
+        if not (np.isfinite(temperature) and temperature > 0):
+            raise ValueError("temperature must be finite and > 0")
+        loss = torch.empty(nq, dtype=torch.float32, device=self.device)
+        tscore = torch.empty(nq, dtype=torch.float32, device=self.device)
+        rank = torch.empty(nq, dtype=torch.int64, device=self.device)
+        bound = torch.empty(nq, dtype=torch.float32, device=self.device)
+        cand = torch.empty((nq, K), dtype=torch.int64, device=self.device)
+        gq = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device) if grad else None
+        if nq > 0:
+            with torch.cuda.device(self.device):
+                check(self._L.cwq_rank_ce_topk(self._h, _ptr(q), nq, _ptr(t), temperature, K, _ptr(loss),
+                                               _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank), _ptr(bound),
+                                               _ptr(cand), _stream(self.device)))
+        return loss, gq, tscore, rank, bound, cand
 
     def node_logprob(self, q, full=False):
         """Per-node log-likelihood in BFS order: lp' (full=False) or log_prob (full=True)."""

@@ -352,7 +352,17 @@ class CobwebWrapper:
             return self._index.rank_scores(queries)
         return self._index.rank_scores(queries, level_weights)
 
-    def cobweb_ranking_loss(self, queries, labels, temperature=1.0, reduction="mean", level_weights=None):
+    def cobweb_score_candidates(self, queries, sentence_ids):
+        """[Q, D] queries and [Q, m] sentence ids (from another retriever, a hard-negative list,
+        ...) -> [Q, m] Fast scores, the values cobweb_rank_scores_batch has in those columns,
+        without the [Q, n_sentences] block (no reference counterpart; cwq_score_pairs).  -inf
+        for an id of -1, an id out of range and a sentence outside the tree.  Differentiable
+        with respect to `queries` like cobweb_rank_scores_batch."""
+        self.build_prediction_index()
+        return self._index.score_pairs(queries, sentence_ids)
+
+    def cobweb_ranking_loss(self, queries, labels, temperature=1.0, reduction="mean", level_weights=None,
+                            top_k=None):
         """FixedDocsRankingLoss.forward (src/training/cobweb_query_train.py:104-126) for a
         block: [Q, D] query embeddings and [Q] labels (sentence ids) -> CrossEntropyLoss(
         cobweb_rank_scores(q) / temperature, label) averaged over the batch ("mean", the
@@ -361,10 +371,20 @@ class CobwebWrapper:
         backward stream when a gradient is wanted).
         level_weights: the loss under these level weights (see cobweb_rank_scores_batch); an
         nn.Parameter here is learned by any torch optimiser against the fixed index, and
-        written back once with set_level_weights(w.tolist())."""
+        written back once with set_level_weights(w.tolist()).
+        top_k: the cross-entropy over the exact top_k retrieved sentences plus the label instead
+        of over all sentences (hard-negative training at retrieval speed; cwq_rank_ce_topk,
+        DESIGN §4.18).  Not together with level_weights: retrieval reads the baked weights."""
         if reduction not in ("mean", "sum", "none"):
             raise ValueError('reduction must be "mean", "sum" or "none"')
+        if top_k is not None and level_weights is not None:
+            raise ValueError("top_k and level_weights do not go together: retrieval reads the level weights baked "
+                             "into the index (set_level_weights)")
         self.build_prediction_index()
+        if top_k is not None:
+            from .autograd import rank_ce_topk_autograd
+            loss = rank_ce_topk_autograd(self._index, torch.as_tensor(queries), labels, top_k, temperature)[0]
+            return loss if reduction == "none" else loss.mean() if reduction == "mean" else loss.sum()
         from .autograd import rank_ce_autograd
         if level_weights is None:
             loss, _, _ = rank_ce_autograd(self._index, torch.as_tensor(queries), labels, temperature)
@@ -372,14 +392,22 @@ class CobwebWrapper:
             loss, _, _ = rank_ce_autograd(self._index, torch.as_tensor(queries), labels, temperature, level_weights)
         return loss if reduction == "none" else loss.mean() if reduction == "mean" else loss.sum()
 
-    def cobweb_target_ranks(self, queries, labels, level_weights=None):
+    def cobweb_target_ranks(self, queries, labels, level_weights=None, top_k=None):
         """evaluate()'s two per-query numbers (src/training/cobweb_query_train.py:213-304)
         without forming a ranking: (rank [Q] int64, the 1-based position of the label in the
         Fast ranking -- -1 for a label outside the tree --, true_score [Q]).
         level_weights: the ranks under these level weights (recall / MRR of a schedule sweep
-        against a fixed index)."""
+        against a fixed index).
+        top_k: ranks from one top_k retrieval instead of a scan of all leaves, capped at
+        top_k + 1 ("at least top_k + 1"); not together with level_weights."""
+        if top_k is not None and level_weights is not None:
+            raise ValueError("top_k and level_weights do not go together: retrieval reads the level weights baked "
+                             "into the index (set_level_weights)")
         self.build_prediction_index()
         with torch.no_grad():
+            if top_k is not None:
+                _, _, tscore, rank, _, _ = self._index.rank_ce_topk(torch.as_tensor(queries).detach(), labels, top_k)
+                return rank, tscore
             if level_weights is None:
                 _, _, tscore, rank = self._index.rank_ce(torch.as_tensor(queries).detach(), labels)
             else:
