@@ -470,6 +470,59 @@ int cwq_score_topk_masked_multi(cwq_index* idx, const cwq_mask* const* masks, in
 int cwq_last_mask_multi_stats(const cwq_index* idx, int64_t* out8);
 
 /*
+ * Masked ranking loss (no reference counterpart): cwq_rank_ce and
+ * cwq_rank_ce_topk over an allowed sentence set.  With A the sentences that the mask allows
+ * and that are in the tree, and T the temperature:
+ *   loss[q]  = logsumexp_{s in A}(score(q, s) / T) - score(q, target[q]) / T
+ *   rank[q]  = 1 + the sentences of A before the target in cwq_score_topk's order (key
+ *              descending, then lower node index, then lower sentence id): rank <= k exactly
+ *              when cwq_score_topk_masked(k) returns the target
+ *   target_score[q] = the bits cwq_rank_scores writes for the target
+ * A target that is not in A (not allowed, out of range, or not in the tree) is handled as
+ * cwq_rank_ce handles an invalid target: loss +inf, a zero grad_q row, target_score -inf,
+ * rank -1, the other queries undisturbed.  A mask without a live row gives that for every
+ * query, without a scan.  No float atomics: the outputs are bit-identical from run to run, and
+ * a query's outputs are the same alone, in any batch and under any workspace chunking.
+ *
+ * cwq_rank_ce_masked: arguments as cwq_rank_ce plus the mask (grad_q, target_score and rank
+ * may be NULL).  Two paths, chosen from the mask alone (never from nq):
+ *   full      cwq_rank_ce's pipeline -- the exact scan and the backward stream over every
+ *             row -- with each row's sentence count replaced by its allowed count (computed
+ *             per call from the mask's bitset; the mask holds no counts)
+ *   gathered  both streams over the mask's live rows only: the gathered exact scan writes
+ *             the live rows' keys (the exact scan's bits) into key lines pre-filled with
+ *             -inf, and the backward walks the mask's row lists
+ * loss, target_score and rank are bit-identical between the paths (the [row]-indexed key and
+ * coefficient arrays are dense on both); grad_q may differ by summation order.  The gathered
+ * path is taken when the live rows are fewer than 0.55 of the leaf-class rows (fitted on flat
+ * 1M x 768 and 100k x 768).  Env CWQ_MASK_CE_PATH, read per call: 0 / unset
+ * automatic, 1 full, 2 gathered.  cwq_last_mask_stats then reports [path code 5 (full) or 6
+ * (gathered), 0, 0, live rows of the mask].
+ *
+ * cwq_rank_ce_topk_masked: cwq_rank_ce_topk with the candidates from the masked retrieval.
+ *   masks, n_masks, mask_of_query  as cwq_score_topk_masked_multi (mask_of_query: HOST
+ *             memory, nq entries); mask_of_query may be NULL when n_masks == 1
+ * C = the target plus what cwq_score_topk_masked(K) (several masks:
+ * cwq_score_topk_masked_multi) returns; cand_ids is that row bit for bit;
+ *   tail_bound = log1p((n_allowed(q) - |C|) exp((s_K - m) / T) / z)
+ * with the query's own mask's allowed count; rank is exact inside the top-K, else K + 1.  Row
+ * i of a call over several masks equals the single-mask call on query i alone, bit for bit in
+ * every output.  The call synchronises `stream`.
+ *
+ * Both: CWQ_ERR_ARG with a message, before any device work, for a NULL idx / mask(s) / q /
+ * target / loss, a mask of another index, nq < 0, K < 1, a temperature that is not finite or
+ * not > 0, n_masks < 1, a NULL mask_of_query with n_masks != 1, an entry of mask_of_query
+ * outside [0, n_masks), K + 1 > 4096 with grad_q.  nq == 0 is a no-op.
+ */
+int cwq_rank_ce_masked(cwq_index* idx, const cwq_mask* m, const float* q, int64_t nq, const int64_t* target,
+                       float temperature, float* loss, float* grad_q, float* target_score, int64_t* rank,
+                       void* stream);
+int cwq_rank_ce_topk_masked(cwq_index* idx, const cwq_mask* const* masks, int32_t n_masks,
+                            const int32_t* mask_of_query, const float* q, int64_t nq, const int64_t* target,
+                            float temperature, int32_t K, float* loss, float* grad_q, float* target_score,
+                            int64_t* rank, float* tail_bound, int64_t* cand_ids, void* stream);
+
+/*
  * Group pruning of the Fast query (clustered trees whose rows are
  * group-centred, every level weight >= 0): per (query, depth-1 group) a certified upper
  * bound of every key in the group; the exact internal pass runs for each query's best group

@@ -59,6 +59,8 @@ SIGNATURES = {
     "cwq_last_mask_stats": (_c.c_int, [_P, _P]),
     "cwq_score_topk_masked_multi": (_c.c_int, [_P, _P, _I32, _P, _P, _I64, _I32, _P, _P, _P]),
     "cwq_last_mask_multi_stats": (_c.c_int, [_P, _P]),
+    "cwq_rank_ce_masked": (_c.c_int, [_P, _P, _P, _I64, _P, _c.c_float, _P, _P, _P, _P, _P]),
+    "cwq_rank_ce_topk_masked": (_c.c_int, [_P, _P, _I32, _P, _P, _I64, _P, _c.c_float, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "cwq_score_topk_host": (_c.c_int, [_P, _P, _I64, _I32, _P, _P, _P]),
     "cwq_categorize_host": (_c.c_int, [_P, _P, _I64, _I32, _I64, _P, _P, _P, _P]),
     "cwq_whiten": (_c.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _I32, _P, _P, _P]),

@@ -66,8 +66,10 @@ class RankCE(torch.autograd.Function):
     them: the backward is torch arithmetic, no library call, so the index needs no pin."""
 
     @staticmethod
-    def forward(ctx, q, index, target, temperature, need, w=None, need_w=False):
-        if w is None:
+    def forward(ctx, q, index, target, temperature, need, w=None, need_w=False, mask=None):
+        if mask is not None:
+            loss, gq, tscore, rank, *gw = index.rank_ce(q.detach(), target, temperature, grad=need, mask=mask)
+        elif w is None:
             loss, gq, tscore, rank, *gw = index.rank_ce(q.detach(), target, temperature, grad=need)
         else:
             loss, gq, tscore, rank, *gw = index.rank_ce(q.detach(), target, temperature, grad=need,
@@ -83,7 +85,7 @@ class RankCE(torch.autograd.Function):
         saved = list(ctx.saved_tensors)
         gq = saved.pop(0) * grad_loss[:, None] if ctx.need else None
         gw = (saved.pop(0) * grad_loss[:, None]).sum(0) if ctx.need_w else None
-        return gq, None, None, None, None, gw, None
+        return gq, None, None, None, None, gw, None, None
 
 
 def _weights(index, w):
@@ -97,10 +99,14 @@ def _weights(index, w):
     return w.to(index.device, torch.float32).contiguous()
 
 
-def rank_ce_autograd(index, q, target, temperature=1.0, level_weights=None):
+def rank_ce_autograd(index, q, target, temperature=1.0, level_weights=None, mask=None):
     """Differentiable per-query loss of index.rank_ce, with the target's score and rank: the
     device move, the cast and the reshape in front are torch ops, as in rank_scores_autograd.
-    Under torch.no_grad(), or for inputs that do not require grad, no gradient pass runs."""
+    Under torch.no_grad(), or for inputs that do not require grad, no gradient pass runs.
+    mask: the loss over a SentenceMask's allowed sentences (index.rank_ce(mask=...)); not
+    together with level_weights."""
+    if mask is not None and level_weights is not None:
+        raise ValueError("mask and level_weights do not go together (call-time weights are not masked)")
     if q.dim() == 1:
         q = q[None, :]
     if q.dim() != 2 or q.shape[1] != index.dim:
@@ -110,7 +116,7 @@ def rank_ce_autograd(index, q, target, temperature=1.0, level_weights=None):
     # decided here: grad mode is always off inside a Function's forward
     on = torch.is_grad_enabled()
     need = bool(q.requires_grad and on)
-    return RankCE.apply(q, index, target, temperature, need, w, bool(w is not None and w.requires_grad and on))
+    return RankCE.apply(q, index, target, temperature, need, w, bool(w is not None and w.requires_grad and on), mask)
 
 
 def rank_scores_autograd(index, q, level_weights=None):
@@ -169,9 +175,10 @@ class RankCETopK(torch.autograd.Function):
     backward is torch arithmetic; the index is pinned all the same, as RankScores pins it."""
 
     @staticmethod
-    def forward(ctx, q, index, target, K, temperature, need):
+    def forward(ctx, q, index, target, K, temperature, need, mask=None, masks=None, mask_of_query=None):
         ctx.pin = _Pin(index)
-        loss, gq, tscore, rank, bound, cand = index.rank_ce_topk(q.detach(), target, K, temperature, grad=need)
+        loss, gq, tscore, rank, bound, cand = index.rank_ce_topk(q.detach(), target, K, temperature, grad=need,
+                                                                 mask=mask, masks=masks, mask_of_query=mask_of_query)
         ctx.need = need
         ctx.save_for_backward(*([gq] if need else []))
         ctx.mark_non_differentiable(tscore, rank, bound, cand)
@@ -181,7 +188,7 @@ class RankCETopK(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_loss, *_):
         gq = ctx.saved_tensors[0] * grad_loss[:, None] if ctx.need else None
-        return gq, None, None, None, None, None
+        return gq, None, None, None, None, None, None, None, None
 
 
 def _queries_autograd(index, q):
@@ -207,10 +214,10 @@ def pair_scores_autograd(index, q, ids):
     return PairScores.apply(q, index, index._pair_ids(ids, q.shape[0]))
 
 
-def rank_ce_topk_autograd(index, q, target, K, temperature=1.0):
+def rank_ce_topk_autograd(index, q, target, K, temperature=1.0, mask=None, masks=None, mask_of_query=None):
     """Differentiable per-query loss of index.rank_ce_topk with the target's score, its rank, the
     tail bound and the candidate ids (all non-differentiable).  Under torch.no_grad(), or for a
     q that does not require grad, no gradient pass runs."""
     q = _queries_autograd(index, q)
     need = bool(q.requires_grad and torch.is_grad_enabled())
-    return RankCETopK.apply(q, index, target, int(K), float(temperature), need)
+    return RankCETopK.apply(q, index, target, int(K), float(temperature), need, mask, masks, mask_of_query)

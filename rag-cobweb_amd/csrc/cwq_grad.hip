@@ -174,6 +174,7 @@ struct StreamK {
   float* part;           // [nslab_total][nq16][DP]
   int slab_off, nq16;
   int rt;                // dim-major: rows per LDS tile (4 or 8)
+  const int* list;       // LIST: the class's rows to walk, list[0, nrows) (slabs by list position)
 };
 
 // the 16 coefficients of a row: a wave-uniform address (scalar loads)
@@ -188,7 +189,10 @@ __device__ __forceinline__ void load_coef(const float* __restrict__ cf, f2 (&c)[
 // TPR threads share a row (a multiple of 64: the row is wave-uniform), J dims per thread;
 // 256 / TPR row groups take the slab's rows in turn and are summed in group order at the end.
 // DM: dim-major operands, staged through LDS in tiles of a.rt rows (coalesced along rows).
-template <int TPR, int J, bool DM>
+// LIST (the masked loss's gathered backward): positions r_begin .. r_end walk
+// a.list, whose entries are the class rows to read (means and coefficients by row id); a
+// group's row is still wave-uniform.  !LIST is the code without the indirection.
+template <int TPR, int J, bool DM, bool LIST>
 __global__ __launch_bounds__(256) void grad_stream_kernel(const StreamK a) {
   extern __shared__ float lds[];
   constexpr int RG = 256 / TPR;
@@ -222,19 +226,21 @@ __global__ __launch_bounds__(256) void grad_stream_kernel(const StreamK a) {
     constexpr int U = 4;   // rows in flight per group
     for (int r = r_begin + grp; r < r_end; r += RG * U) {
       float m[U][J];
+      int row[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int rr = r + u * RG;
+        row[u] = LIST ? (rr < r_end ? a.list[rr] : 0) : rr;
 #pragma unroll
         for (int j = 0; j < J; ++j)
-          m[u][j] = (rr < r_end && dok[j]) ? a.M[(size_t)rr * a.DP + d0 + tl + TPR * j] : 0.f;
+          m[u][j] = (rr < r_end && dok[j]) ? a.M[(size_t)row[u] * a.DP + d0 + tl + TPR * j] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int rr = r + u * RG;
         if (rr < r_end) {
           f2 c[kGQ / 2];
-          load_coef(coef + (size_t)rr * kGQ, c);
+          load_coef(coef + (size_t)row[u] * kGQ, c);
 #pragma unroll
           for (int j = 0; j < J; ++j) {
             const f2 mm = f2{m[u][j], m[u][j]};
@@ -252,9 +258,10 @@ __global__ __launch_bounds__(256) void grad_stream_kernel(const StreamK a) {
     const int lr = tid & (RT - 1), ld0 = tid / RT, lstep = 256 / RT;
     for (int R0 = r_begin; R0 < r_end; R0 += RT) {
       __syncthreads();   // the previous tile's readers (and nothing before the first)
+      const int srow = LIST ? (R0 + lr < r_end ? a.list[R0 + lr] : 0) : R0 + lr;
       for (int d = ld0; d < DPc; d += lstep) {
         const int rr = R0 + lr;
-        const size_t o = (size_t)(d0 + d) * a.ld + rr;
+        const size_t o = (size_t)(d0 + d) * a.ld + srow;
         sA[lr * st + d] = rr < r_end ? a.A[o] : 0.f;
         sB[lr * st + d] = rr < r_end ? a.B[o] : 0.f;
       }
@@ -263,7 +270,7 @@ __global__ __launch_bounds__(256) void grad_stream_kernel(const StreamK a) {
         const int rr = R0 + t;
         if (rr >= r_end) break;
         f2 c[kGQ / 2];
-        load_coef(coef + (size_t)rr * kGQ, c);
+        load_coef(coef + (size_t)(LIST ? a.list[rr] : rr) * kGQ, c);
 #pragma unroll
         for (int j = 0; j < J; ++j) {
           if (!dok[j]) continue;
@@ -352,16 +359,16 @@ __global__ __launch_bounds__(1024) void grad_reduce_kernel(const float* __restri
   }
 }
 
-template <int TPR, int J, bool DM>
+template <int TPR, int J, bool DM, bool LIST>
 hipError_t launch_stream_tj(const StreamK& k, dim3 grid, size_t ldsb, hipStream_t s) {
-  hipLaunchKernelGGL((grad_stream_kernel<TPR, J, DM>), grid, dim3(256), ldsb, s, k);
+  hipLaunchKernelGGL((grad_stream_kernel<TPR, J, DM, LIST>), grid, dim3(256), ldsb, s, k);
   return hipGetLastError();
 }
 
-template <bool DM>
+template <bool DM, bool LIST>
 hipError_t launch_stream_class(const StreamK& k, int tpr, int j, dim3 grid, size_t ldsb, hipStream_t s) {
 #define CWQ_GRAD_CASE(T, JJ) \
-  if (tpr == T && j == JJ) return launch_stream_tj<T, JJ, DM>(k, grid, ldsb, s);
+  if (tpr == T && j == JJ) return launch_stream_tj<T, JJ, DM, LIST>(k, grid, ldsb, s);
   CWQ_GRAD_CASE(64, 1) CWQ_GRAD_CASE(64, 2) CWQ_GRAD_CASE(64, 3) CWQ_GRAD_CASE(64, 4)
   CWQ_GRAD_CASE(128, 1) CWQ_GRAD_CASE(128, 2) CWQ_GRAD_CASE(128, 3) CWQ_GRAD_CASE(128, 4)
   CWQ_GRAD_CASE(256, 1) CWQ_GRAD_CASE(256, 2) CWQ_GRAD_CASE(256, 3) CWQ_GRAD_CASE(256, 4)
@@ -452,9 +459,14 @@ hipError_t launch_grad_stream(const GradStreamArgs& g, hipStream_t s) {
   const int nslab = (g.nrows + g.rows_per_slab - 1) / g.rows_per_slab;
   const dim3 grid((unsigned)nslab, (unsigned)g.qtiles, (unsigned)((g.DP + kGradDimChunk - 1) / kGradDimChunk));
   const size_t red = tpr < 256 ? (size_t)kGQ * tpr * j * 4 : 0;
-  if (g.M) return launch_stream_class<false>(k, tpr, j, grid, red, s);
+  k.list = g.list;
+  if (g.M)
+    return g.list ? launch_stream_class<false, true>(k, tpr, j, grid, red, s)
+                  : launch_stream_class<false, false>(k, tpr, j, grid, red, s);
   const size_t tile = (size_t)2 * k.rt * (dpc + 1) * 4;
-  return launch_stream_class<true>(k, tpr, j, grid, tile > red ? tile : red, s);
+  const size_t ldsb = tile > red ? tile : red;
+  return g.list ? launch_stream_class<true, true>(k, tpr, j, grid, ldsb, s)
+                : launch_stream_class<true, false>(k, tpr, j, grid, ldsb, s);
 }
 
 hipError_t launch_grad_reduce(const float* part, int nslab, int qtiles, int nq, int DP, int D, float* out,

@@ -1,7 +1,7 @@
 // The query library's host layer behind the C ABI: the handle (struct cwq_index), the per-call
 // scopes, the query chunk, and the declarations of the host functions that cross a file.
-// Host only: included by cwq_api.hip, cwq_rank.hip, cwq_fitcalls.hip, cwq_maskcalls.hip and cwq_sparsecalls.hip and by
-// nothing else; the
+// Host only: included by cwq_api.hip, cwq_rank.hip, cwq_fitcalls.hip, cwq_maskcalls.hip, cwq_sparsecalls.hip and
+// cwq_masklosscalls.hip and by nothing else; the
 // kernel sources share cwq_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -287,6 +287,9 @@ struct cwq_index {
   // cwq_score_topk_masked_multi, masks run as calls of their own: one mask's gathered queries
   // and results (the single-mask call uses mk and fb itself)
   GrowBuf mg{GrowBuf::kDevice, 1 << 16, "per-query masks: sub-call buffers hipMalloc failed ("};
+  // cwq_rank_ce_topk_masked: the slot table, the masked top-K result, the target's key and the
+  // backward's list (the masked Fast call it runs uses mk, fb and mg itself)
+  GrowBuf ml{GrowBuf::kDevice, 1 << 16, "masked loss buffers hipMalloc failed ("};
   int64_t mask_stats[4] = {0, 0, 0, 0};   // cwq_last_mask_stats
   int64_t mask_multi_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // cwq_last_mask_multi_stats
 
@@ -344,7 +347,7 @@ struct cwq_index {
     if (ws_ev_live) (void)hipEventSynchronize(ws_ev);
     if (ws_ev) (void)hipEventDestroy(ws_ev);
     for (void* p : allocs) (void)hipFree(p);
-    for (GrowBuf* b : {&ws, &fb, &fb2, &mk, &mg, &hflags, &hq, &dq, &hout}) b->release();
+    for (GrowBuf* b : {&ws, &fb, &fb2, &mk, &mg, &ml, &hflags, &hq, &dq, &hout}) b->release();
   }
 };
 
@@ -472,5 +475,31 @@ int64_t chunk_queries(const cwq_index* ix, int64_t nq, size_t per_query_extra, b
 void topk_begin(cwq_index* ix);
 int score_topk_unmasked(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,
                         hipStream_t s);
+
+// cwq_maskcalls.hip: the masked Fast call for a caller that holds the handle (QueryCall): query i
+// restricted to masks[mask_of_query[i]] (host array; null: masks[0] for every query), the path
+// rules and stats of cwq_score_topk_masked / cwq_score_topk_masked_multi.  Arguments are checked
+// by the caller.
+int masked_topk_locked(cwq_index* ix, const cwq_mask* const* masks, int32_t n_masks, const int32_t* mask_of_query,
+                       const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores, hipStream_t s, int rc0 = 0);
+
+// cwq_sparsecalls.hip: scores[q][j] of given sentences and the gradient of their weighted sum,
+// chunk by chunk, for a caller that holds the handle
+int pairs_forward(cwq_index* ix, const float* q, int64_t nq, const int64_t* ids, int m, int64_t ld_ids, float* out,
+                  int64_t ld_out, hipStream_t s);
+int pairs_backward(cwq_index* ix, const float* q, int64_t nq, const int64_t* ids, int m, const float* g, float* grad_q,
+                   hipStream_t s);
+
+// cwq_rank.hip (the dense backward's plan and carve, shared with the masked loss)
+// The backward's launch plan: slabs, leaf-sum pieces, threads per node and workspace bytes per
+// query -- functions of the index alone (a query's gradient is the same in any batch).
+struct GradPlan {
+  int rps, ns_iso, ns_an, ns_int, nslab, nsplit, P;
+  std::vector<int> lv;
+  size_t per_q;
+};
+GradPlan grad_plan(const cwq_index* ix);
+// The coefficient arrays and the partial tiles of one chunk (nq16 * per_q bytes + 8 * 256).
+float* grad_carve(const cwq_index* ix, const GradPlan& gp, Bump& b, int nqc, int qtiles, GradCoefArgs& ca);
 
 }  // namespace cwq

@@ -82,6 +82,8 @@ struct ScanArgs {
   int nslab_total;
   int slab_off;
   int K;
+  float* rowkey;        // the key-writing form (launch_mask_scan_keys): [nq][ldr] by global leaf-row id
+  int64_t ldr;
 };
 
 // Heap entry of the categorize simulation.
@@ -937,6 +939,9 @@ struct GradStreamArgs {
   int nrows, rows_per_slab;
   const float* coef; int ncoef, coef_base;
   float* part; int slab_off;
+  // the list form (the masked loss's gathered backward): the class's rows list[0, nrows)
+  // (ascending class row ids) instead of rows 0 .. nrows - 1; slabs are cut by list position.  null: every row
+  const int* list;
 };
 hipError_t launch_grad_stream(const GradStreamArgs& g, hipStream_t s);
 // out[q][d] = -sum over the slabs in index order, d < D
@@ -958,11 +963,22 @@ struct CeArgs {
   float* pm; float* pz; int* pc;      // [qtiles * 16][npart] partials
   float* loss; float* tscore; int64_t* rank;   // [nq]; tscore / rank may be null
   float2* mz; int* rtq;               // [qtiles * 16]: (m, 1/z), the target's row (-1: invalid)
+  // the masked loss (cwq_rank_ce_masked): cnt[r] = the row's allowed sentences
+  // (launch_mask_counts) stands for its sentence count and `bits` decides the target's validity
+  // and its place inside its own row.  Both null: the unmasked loss
+  const int* cnt; const uint32_t* bits;
 };
 // ce_part_kernel + ce_final_kernel: the partials, then loss / tscore / rank / mz / rtq
 hipError_t launch_ce_reduce(const CeArgs& a, hipStream_t s);
 // ce_coef_kernel: coefL / hL [qtiles][NL][16] of the loss's gradient (grad_rows_kernel's layout)
 hipError_t launch_ce_coef(const CeArgs& a, const RowMeta* meta, int NL_iso, float* coefL, float* hL, hipStream_t s);
+// cnt[r] = live[r] ? the sentences of row r that `bits` allows : 0
+hipError_t launch_mask_counts(const uint8_t* live, const int64_t* sent_ptr, const int64_t* sent_ids,
+                              const uint32_t* bits, int NL, int* cnt, hipStream_t s);
+// the result of an invalid target for every query: loss +inf, a zero grad_q row, score -inf,
+// rank -1 (grad_q / tscore / rank may be null)
+hipError_t launch_ce_invalid(int64_t nq, int D, float* loss, float* grad_q, float* tscore, int64_t* rank,
+                             hipStream_t s);
 
 // ---- sparse differentiable scores (cwq_sparse.hip) ----
 constexpr int kSparseMaxM = 4096;        // entries per query of the sparse backward (its LDS lists)
@@ -996,6 +1012,7 @@ struct SparseGradArgs {
 };
 hipError_t launch_sparse_grad(SparseGradArgs a, hipStream_t s);
 // the truncated loss over the top-K list and the target (one wave per query)
+struct MaskSlot;
 struct SparseCeArgs {
   int nq, K, NL; float invT;
   const int64_t* top_ids; const float* top_scores;   // [nq][K], cwq_score_topk's
@@ -1003,6 +1020,10 @@ struct SparseCeArgs {
   int64_t n_sent; const int* row_of_sent; const int64_t* sent_ptr;
   float* loss; float* tscore_out; int64_t* rank; float* tail_bound; int64_t* cand_ids;
   int64_t* bid; float* bg;                           // [nq][K + 1] the backward's list, or null
+  // the masked form (cwq_rank_ce_topk_masked): query q's mask is slots[qslot[q]]
+  // (qslot null: slots[0]); a target must be allowed, and the tail counts the mask's allowed
+  // sentences.  slots null: the unmasked loss
+  const MaskSlot* slots; const int* qslot;
 };
 hipError_t launch_ce_topk(const SparseCeArgs& a, hipStream_t s);
 
@@ -1095,6 +1116,8 @@ struct MaskScanArgs {
   int nslab_total;
   int slab_off;
   int K;
+  float* rowkey;        // the key-writing form (launch_mask_scan_keys): [nq][ldr] by global leaf-row id
+  int64_t ldr;
 };
 // live flags of all leaf-class rows, the two ascending row lists with their counts
 // (counts2[0] isotropic, [1] anisotropic) and the number of allowed sentences in the tree;
@@ -1109,6 +1132,11 @@ constexpr int mask_scan_tile(bool shq) { return shq ? 256 : 64; }             //
 constexpr int mask_scan_lists(bool shq) { return shq ? kWavesPerWG : 1; }     // partial lists per slab and query
 hipError_t launch_mask_scan(bool iso, int kl, bool shq, const float* X, const float* A, const float* B,
                             const MaskScanArgs& a, int nslab, hipStream_t s);
+// The key-writing form (the masked loss's gathered forward): the same arithmetic and
+// bits, rowkey[q][seg_base + row] for the listed rows instead of top-K lists (pkey / paux / prow,
+// nslab_total, slab_off and K are not read)
+hipError_t launch_mask_scan_keys(bool iso, bool shq, const float* X, const float* A, const float* B,
+                                 const MaskScanArgs& a, int nslab, hipStream_t s);
 hipError_t launch_mask_merge_expand(const float* pkey, const float* paux, const int* prow, int nq, int nent, int K,
                                     int k, const int64_t* sent_ptr, const int64_t* sent_ids, const uint32_t* bits,
                                     int64_t* ids, float* scores, hipStream_t s);

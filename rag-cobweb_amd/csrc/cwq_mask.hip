@@ -164,7 +164,9 @@ constexpr int kMsStride = kMsDC + 1;   // LDS floats per row
 // GRP (the grouped form): the slab, the row list, the queries and the lists come
 // from the workgroup's work item work[blockIdx.x] instead of blockIdx.x and `a` (one launch per
 // segment and form serves every mask of a call); everything else is the same code.
-template <bool ISO, int KL, bool SHQ, bool GRP>
+// KEYS (the masked loss's gathered forward): the keys of the listed rows go to
+// a.rowkey[q][global row] instead of into top-K lists -- the same arithmetic, the same bits.
+template <bool ISO, int KL, bool SHQ, bool GRP, bool KEYS = false>
 __global__ __launch_bounds__(256) void mask_scan_kernel(const float* __restrict__ X, const float* __restrict__ A,
                                                         const float* __restrict__ B, const MaskScanArgs a,
                                                         const MaskWork* __restrict__ work) {
@@ -304,6 +306,10 @@ __global__ __launch_bounds__(256) void mask_scan_kernel(const float* __restrict_
           lp = -0.5f * (md.logdet + a.dconst + acc[l][qi]);
           key = fmaf(pp, md.invL, md.cw * lp);
         }
+        if constexpr (KEYS) {
+          if (vrow[l]) a.rowkey[(size_t)q * a.ldr + rid] = key;
+          continue;
+        }
         if (!vrow[l]) key = -CWQ_INF;
         const int r = qi / QPR;
         const int gq = qi % QPR;
@@ -322,6 +328,7 @@ __global__ __launch_bounds__(256) void mask_scan_kernel(const float* __restrict_
     }
   }
 
+  if constexpr (KEYS) return;
   const int slot = lane & (KL - 1);
   const int lst = SHQ ? slab * kWavesPerWG + wave : slab;   // shared queries: every wave holds its own list
 #pragma unroll
@@ -363,6 +370,20 @@ hipError_t launch_mask_scan(bool iso, int kl, bool shq, const float* X, const fl
     else { if (shq) CWQ_MS(false, 64, true); else CWQ_MS(false, 64, false); }
   }
 #undef CWQ_MS
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_scan_keys(bool iso, bool shq, const float* X, const float* A, const float* B,
+                                 const MaskScanArgs& a, int nslab, hipStream_t s) {
+  if (a.n_live <= 0 || nslab <= 0) return hipSuccess;
+  if (a.DP % kMsDC || a.rows_per_slab % mask_scan_tile(shq) || (int64_t)nslab * a.rows_per_slab < a.n_live ||
+      (int64_t)a.n_qblocks * (shq ? kXQ : kXQ * kWavesPerWG) < a.nq || !a.rowkey || !a.list)
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((int64_t)nslab * a.n_qblocks)), block(256);
+#define CWQ_MSK(ISO_, SHQ_) hipLaunchKernelGGL((mask_scan_kernel<ISO_, 16, SHQ_, false, true>), grid, block, 0, s, X, A, B, a, (const MaskWork*)nullptr)
+  if (iso) { if (shq) CWQ_MSK(true, true); else CWQ_MSK(true, false); }
+  else { if (shq) CWQ_MSK(false, true); else CWQ_MSK(false, false); }
+#undef CWQ_MSK
   return hipGetLastError();
 }
 

@@ -716,6 +716,43 @@ int masked_multi_impl(cwq_index* ix, std::vector<MultiGroup>& gs, const float* q
 
 }  // namespace
 
+namespace cwq {
+// The masked Fast call under the handle's lock (cwq_handle.h); rc0: the caller's ws_begin result,
+// returned once the stats are reset, as the entry points did.
+int masked_topk_locked(cwq_index* ix, const cwq_mask* const* masks, int32_t n_masks, const int32_t* mask_of_query,
+                       const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores, hipStream_t s, int rc0) {
+  // counting sort by distinct mask (a mask named by two slots is one group)
+  std::vector<int> group_of_slot((size_t)n_masks, -1);
+  std::vector<MultiGroup> gs;
+  {
+    std::map<const cwq_mask*, int> seen;
+    std::vector<char> used((size_t)n_masks, 0);
+    if (!mask_of_query) used[0] = 1;
+    for (int64_t i = 0; mask_of_query && i < nq; ++i) used[mask_of_query[i]] = 1;
+    for (int32_t i = 0; i < n_masks; ++i) {
+      if (!used[i]) continue;
+      auto it = seen.find(masks[i]);
+      if (it == seen.end()) {
+        it = seen.emplace(masks[i], (int)gs.size()).first;
+        gs.push_back(MultiGroup());
+        gs.back().m = masks[i];
+      }
+      group_of_slot[i] = it->second;
+    }
+    if (gs.size() > 1)
+      for (int64_t i = 0; i < nq; ++i) gs[group_of_slot[mask_of_query[i]]].qi.push_back((int)i);
+  }
+  topk_begin(ix);
+  for (int64_t& t : ix->mask_stats) t = 0;
+  for (int64_t& t : ix->mask_multi_stats) t = 0;
+  ix->mask_multi_stats[6] = (int64_t)gs.size();
+  if (rc0) return rc0;
+  // one mask for every query: the single-mask call, its path and its stats
+  if (gs.size() == 1) return masked_single_locked(ix, gs[0].m, q, nq, k, ids, scores, s);
+  return masked_multi_impl(ix, gs, q, nq, k, ids, scores, s);
+}
+}  // namespace cwq
+
 extern "C" int cwq_score_topk_masked_multi(cwq_index* ix, const cwq_mask* const* masks, int32_t n_masks,
                                            const int32_t* mask_of_query, const float* q, int64_t nq, int32_t k,
                                            int64_t* ids, float* scores, void* stream) {
@@ -732,41 +769,9 @@ extern "C" int cwq_score_topk_masked_multi(cwq_index* ix, const cwq_mask* const*
       return fail(CWQ_ERR_ARG, "mask_of_query[" + std::to_string(i) + "] = " + std::to_string(mask_of_query[i]) +
                                    " is outside [0, " + std::to_string(n_masks) + ")");
   if (nq == 0) return CWQ_OK;
-  // counting sort by distinct mask (a mask named by two slots is one group)
-  std::vector<int> group_of_slot((size_t)n_masks, -1);
-  std::vector<MultiGroup> gs;
-  {
-    std::map<const cwq_mask*, int> seen;
-    std::vector<char> used((size_t)n_masks, 0);
-    for (int64_t i = 0; i < nq; ++i) used[mask_of_query[i]] = 1;
-    for (int32_t i = 0; i < n_masks; ++i) {
-      if (!used[i]) continue;
-      auto it = seen.find(masks[i]);
-      if (it == seen.end()) {
-        it = seen.emplace(masks[i], (int)gs.size()).first;
-        gs.push_back(MultiGroup());
-        gs.back().m = masks[i];
-      }
-      group_of_slot[i] = it->second;
-    }
-    for (int64_t i = 0; i < nq; ++i) gs[group_of_slot[mask_of_query[i]]].qi.push_back((int)i);
-  }
-  if (gs.size() == 1) {   // one mask for every query: the single-mask call, its path and its stats
-    {
-      std::lock_guard<std::mutex> lk(ix->mu);
-      for (int64_t& t : ix->mask_multi_stats) t = 0;
-      ix->mask_multi_stats[6] = 1;
-    }
-    return cwq_score_topk_masked(ix, gs[0].m, q, nq, k, ids, scores, stream);
-  }
   hipStream_t s = (hipStream_t)stream;
   QueryCall call(ix, nq, s);
-  topk_begin(ix);
-  for (int64_t& t : ix->mask_stats) t = 0;
-  for (int64_t& t : ix->mask_multi_stats) t = 0;
-  ix->mask_multi_stats[6] = (int64_t)gs.size();
-  if (call.rc) return call.rc;
-  return masked_multi_impl(ix, gs, q, nq, k, ids, scores, s);
+  return masked_topk_locked(ix, masks, n_masks, mask_of_query, q, nq, k, ids, scores, s, call.rc);
 }
 
 extern "C" int cwq_last_mask_multi_stats(const cwq_index* ix, int64_t* out) {

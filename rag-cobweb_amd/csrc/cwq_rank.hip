@@ -68,15 +68,8 @@ extern "C" int cwq_rank_scores_w(cwq_index* ix, const float* q, int64_t nq, cons
   return rank_scores_impl(ix, q, nq, level_w, n_w, out, stream);
 }
 
-namespace {
-// The backward's launch plan: slabs, leaf-sum pieces, threads per node and workspace bytes per
-// query -- functions of the index alone (a query's gradient is the same in any batch).
-struct GradPlan {
-  int rps, ns_iso, ns_an, ns_int, nslab, nsplit, P;
-  std::vector<int> lv;
-  size_t per_q;
-};
-
+namespace cwq {
+// The backward's launch plan (GradPlan, cwq_handle.h; shared with cwq_masklosscalls.hip)
 GradPlan grad_plan(const cwq_index* ix) {
   GradPlan g;
   const int NL = ix->NL, NI = ix->NI;
@@ -127,6 +120,9 @@ float* grad_carve(const cwq_index* ix, const GradPlan& gp, Bump& b, int nqc, int
   ca.coefI = b.take<float>(nq16 * std::max(NI, 1));
   return b.take<float>(nq16 * (size_t)gp.nslab * ix->DP);
 }
+}  // namespace cwq
+
+namespace {
 
 // The streaming reduction over the three row classes and the slab sum, from the coefficients.
 int grad_streams(const cwq_index* ix, const GradPlan& gp, const GradCoefArgs& ca, float* part, const float* q, int nqc,

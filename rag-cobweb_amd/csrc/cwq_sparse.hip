@@ -263,7 +263,15 @@ __global__ __launch_bounds__(64) void ce_topk_kernel(const SparseCeArgs a) {
   const int64_t* __restrict__ tid = a.top_ids + q * K;
   const float* __restrict__ ts = a.top_scores + q * K;
   const int64_t t = a.target[q];
-  const bool tvalid = row_of_id(t, a.n_sent, a.row_of_sent) >= 0;
+  bool tvalid = row_of_id(t, a.n_sent, a.row_of_sent) >= 0;
+  int64_t n_in = 0;   // the sentences the full loss sums over: the tree's, or the mask's allowed ones
+  if (a.slots) {
+    const MaskSlot ms = a.slots[a.qslot ? a.qslot[q] : 0];
+    tvalid = tvalid && ((ms.bits[t >> 5] >> (t & 31)) & 1u);
+    n_in = ms.n_allowed;
+  } else {
+    n_in = a.sent_ptr[a.NL];
+  }
   const float st = tvalid ? a.tscore[q] : -inf;
   float m = st;
   int pos = 0x7fffffff, nv = 0;
@@ -308,7 +316,7 @@ __global__ __launch_bounds__(64) void ce_topk_kernel(const SparseCeArgs a) {
     if (a.rank) a.rank[q] = !tvalid ? -1 : inside ? pos + 1 : K + 1;
     if (a.tail_bound) {
       float b = 0.f;
-      const int64_t rest = a.sent_ptr[a.NL] - nv - (inside ? 0 : 1);   // sentences of the tree outside C
+      const int64_t rest = n_in - nv - (inside ? 0 : 1);   // sentences of the tree (the mask) outside C
       if (tvalid && nv == K && rest > 0) b = log1pf((float)rest * expf((ts[K - 1] - m) * a.invT) * rz);
       a.tail_bound[q] = b;
     }

@@ -3,7 +3,7 @@
 // stream kernel for the internal nodes (cwq_grad.hip).
 #include "cwq_handle.h"
 
-namespace {
+namespace cwq {
 
 // scores[q][j] for the call's queries, chunk by chunk: pad, the exact internal pass (the parents'
 // prefixes, bit for bit the scan's), the gathered keys.
@@ -120,6 +120,10 @@ int pairs_backward(cwq_index* ix, const float* q, int64_t nq, const int64_t* ids
   }
   return CWQ_OK;
 }
+
+}  // namespace cwq
+
+namespace {
 
 int backward_m_check(int64_t m) {
   if (m > kSparseMaxM)

@@ -354,7 +354,8 @@ class CobwebIndex:
     def last_mask_stats(self):
         """The last score_topk(mask=...) call (cwq_last_mask_stats): the path taken (1 over-fetch,
         2 gathered scan, 3 sort for k > 64), the over-fetch k', the queries the over-fetch left
-        short (redone by the gathered scan), the mask's live rows."""
+        short (redone by the gathered scan), the mask's live rows.  After rank_ce(mask=...) the path
+        is 5 (full) or 6 (gathered: both streams over the mask's live rows only)."""
         out = np.zeros(4, np.int64)
         check(self._L.cwq_last_mask_stats(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         return {"path": int(out[0]), "overfetch_k": int(out[1]), "redone_queries": int(out[2]), "live_rows": int(out[3])}
@@ -528,7 +529,12 @@ class CobwebIndex:
                     _ptr(gw) if weight_grad and n_w else None, _stream(self.device)))
         return (out, gw) if weight_grad else out
 
-    def rank_ce(self, q, target, temperature=1.0, grad=False, level_weights=None, weight_grad=False):
+    def _open_mask(self, mask):
+        if not isinstance(mask, SentenceMask) or mask.closed:
+            raise ValueError("mask must be an open SentenceMask (CobwebIndex.sentence_mask)")
+        return mask
+
+    def rank_ce(self, q, target, temperature=1.0, grad=False, level_weights=None, weight_grad=False, mask=None):
         """Cross-entropy ranking loss over all sentence scores (cwq_rank_ce): q [nq, dim],
         target [nq] sentence ids -> (loss [nq] = logsumexp(scores / T) - scores[target] / T,
         grad_q [nq, dim] = d loss / d q or None when grad is False, target_score [nq], rank [nq]
@@ -536,7 +542,14 @@ class CobwebIndex:
         made.  A target outside the tree: loss inf, a zero gradient row, score -inf, rank -1.
         level_weights [n_w]: everything under these level weights instead of the index's own
         (cwq_rank_ce_w); weight_grad=True appends grad_w [nq, n_w] = d loss / d w per query to
-        the returned tuple."""
+        the returned tuple.
+        mask (a SentenceMask of this index): the loss, gradient, score and rank over the mask's
+        allowed sentences only (cwq_rank_ce_masked); a target that is not allowed
+        is an invalid target.  Not together with level_weights (ValueError)."""
+        if mask is not None:
+            self._open_mask(mask)
+            if level_weights is not None or weight_grad:
+                raise ValueError("mask and level_weights do not go together (call-time weights are not masked)")
         q = self._queries(q)
         nq = q.shape[0]
         t = torch.as_tensor(target)
@@ -559,7 +572,11 @@ class CobwebIndex:
         if nq == 0:   # empty tensors have no device pointer to pass
             return (loss, gq, tscore, rank, gw) if weight_grad else (loss, gq, tscore, rank)
         with torch.cuda.device(self.device):
-            if w is None:
+            if mask is not None:
+                check(self._L.cwq_rank_ce_masked(self._h, mask._h, _ptr(q), nq, _ptr(t), temperature, _ptr(loss),
+                                                 _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank),
+                                                 _stream(self.device)))
+            elif w is None:
                 check(self._L.cwq_rank_ce(self._h, _ptr(q), nq, _ptr(t), temperature, _ptr(loss),
                                           _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank), _stream(self.device)))
             else:
@@ -620,12 +637,19 @@ class CobwebIndex:
                                                        _ptr(out), _stream(self.device)))
         return out
 
-    def rank_ce_topk(self, q, target, K, temperature=1.0, grad=False):
+    def rank_ce_topk(self, q, target, K, temperature=1.0, grad=False, mask=None, masks=None, mask_of_query=None):
         """Cross-entropy loss over the exact top-K plus the target (cwq_rank_ce_topk, DESIGN
         §4.18): -> (loss [nq], grad_q [nq, dim] or None when grad is False, target_score [nq],
         rank [nq] int64: exact inside the top-K, else K + 1, tail_bound [nq]: an upper bound of
         rank_ce's loss minus this loss, cand_ids [nq, K]: score_topk's row).  A target outside
-        the tree: loss inf, a zero gradient row, score -inf, rank -1, bound 0."""
+        the tree: loss inf, a zero gradient row, score -inf, rank -1, bound 0.
+        mask, or masks with mask_of_query (as score_topk takes them): the candidates are the
+        masked retrieval's, the tail bound counts the query's own mask's allowed sentences and a
+        target that is not allowed is invalid (cwq_rank_ce_topk_masked)."""
+        if masks is not None and mask is not None:
+            raise ValueError("pass mask= or masks=, not both")
+        if (masks is None) != (mask_of_query is None):
+            raise ValueError("masks= and mask_of_query= go together")
         q = self._queries(q)
         nq = q.shape[0]
         t = torch.as_tensor(target)
@@ -646,7 +670,25 @@ class CobwebIndex:
         bound = torch.empty(nq, dtype=torch.float32, device=self.device)
         cand = torch.empty((nq, K), dtype=torch.int64, device=self.device)
         gq = torch.empty((nq, self.dim), dtype=torch.float32, device=self.device) if grad else None
-        if nq > 0:
+        moq = None
+        if mask is not None:
+            masks = [self._open_mask(mask)]
+        elif masks is not None:
+            masks = list(masks)
+            if not masks or any(not isinstance(m, SentenceMask) or m.closed for m in masks):
+                raise ValueError("masks must be a non-empty sequence of open SentenceMasks (CobwebIndex.sentence_mask)")
+            moq = mask_of_query.detach().cpu().numpy() if torch.is_tensor(mask_of_query) else np.asarray(mask_of_query)
+            if moq.ndim != 1 or moq.shape[0] != nq or moq.dtype.kind not in "iu":
+                raise ValueError(f"mask_of_query must be {nq} integers, one per query")
+            moq = np.ascontiguousarray(moq.clip(-1, 2 ** 31 - 1), dtype=np.int32)   # out of range stays out of range
+        if nq > 0 and masks is not None:
+            handles = (ctypes.c_void_p * len(masks))(*[m._h.value for m in masks])
+            with torch.cuda.device(self.device):
+                check(self._L.cwq_rank_ce_topk_masked(self._h, handles, len(masks), moq.ctypes.data if moq is not None else None,
+                                                      _ptr(q), nq, _ptr(t), temperature, K, _ptr(loss),
+                                                      _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank), _ptr(bound),
+                                                      _ptr(cand), _stream(self.device)))
+        elif nq > 0:
             with torch.cuda.device(self.device):
                 check(self._L.cwq_rank_ce_topk(self._h, _ptr(q), nq, _ptr(t), temperature, K, _ptr(loss),
                                                _ptr(gq) if grad else None, _ptr(tscore), _ptr(rank), _ptr(bound),

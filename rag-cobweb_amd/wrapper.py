@@ -361,8 +361,64 @@ class CobwebWrapper:
         self.build_prediction_index()
         return self._index.score_pairs(queries, sentence_ids)
 
+    def _loss_sets(self, allowed, allowed_sets, set_of_query, level_weights, nq):
+        """The masks of a masked loss / rank call: ([(mask, made here)], set_of_query as a host
+        int64 array or None).  Accepts what cobweb_predict_batch accepts."""
+        if allowed_sets is not None and allowed is not None:
+            raise ValueError("pass allowed= or allowed_sets=, not both")
+        if (allowed_sets is None) != (set_of_query is None):
+            raise ValueError("allowed_sets= and set_of_query= go together")
+        if level_weights is not None:
+            raise ValueError("allowed / allowed_sets and level_weights do not go together: call-time level weights "
+                             "are not masked")
+        if allowed is not None:
+            return [self._mask_for(allowed)], None
+        soq = set_of_query.detach().cpu().numpy() if torch.is_tensor(set_of_query) else np.asarray(set_of_query)
+        if soq.ndim != 1 or soq.shape[0] != nq or soq.dtype.kind not in "iu":
+            raise ValueError(f"set_of_query must be {nq} integers, one per query")
+        sets = list(allowed_sets)
+        if not sets:
+            raise ValueError("allowed_sets must not be empty")
+        if soq.size and (int(soq.min()) < 0 or int(soq.max()) >= len(sets)):
+            raise ValueError(f"set_of_query entries must be in [0, {len(sets)})")
+        made = []
+        try:
+            for a in sets:
+                made.append(self._mask_for(a))
+        except Exception:
+            for m, mine in made:
+                if mine:
+                    m.close()
+            raise
+        return made, soq.astype(np.int64)
+
+    def _masked_rank_ce(self, q, labels, temperature, top_k, made, soq):
+        """(loss, target_score, rank) over the call's masks: the top-K form in one call; the dense
+        form once per set over that set's queries, the rows put back in order."""
+        from .autograd import rank_ce_autograd, rank_ce_topk_autograd
+        masks = [m for m, _ in made]
+        if top_k is not None:
+            if soq is None:
+                out = rank_ce_topk_autograd(self._index, q, labels, top_k, temperature, mask=masks[0])
+            else:
+                out = rank_ce_topk_autograd(self._index, q, labels, top_k, temperature, masks=masks, mask_of_query=soq)
+            return out[0], out[1], out[2]
+        if soq is None:
+            return rank_ce_autograd(self._index, q, labels, temperature, mask=masks[0])
+        lab = torch.as_tensor(labels).reshape(-1)
+        parts, order = [], []
+        for j in np.unique(soq):
+            idx = torch.from_numpy(np.nonzero(soq == j)[0])
+            parts.append(rank_ce_autograd(self._index, q[idx.to(q.device)], lab[idx.to(lab.device)], temperature,
+                                          mask=masks[int(j)]))
+            order.append(idx)
+        if not parts:
+            return rank_ce_autograd(self._index, q, lab, temperature, mask=masks[0])
+        inv = torch.argsort(torch.cat(order)).to(self._index.device)
+        return tuple(torch.cat([p[i] for p in parts])[inv] for i in range(3))
+
     def cobweb_ranking_loss(self, queries, labels, temperature=1.0, reduction="mean", level_weights=None,
-                            top_k=None):
+                            top_k=None, allowed=None, allowed_sets=None, set_of_query=None):
         """FixedDocsRankingLoss.forward (src/training/cobweb_query_train.py:104-126) for a
         block: [Q, D] query embeddings and [Q] labels (sentence ids) -> CrossEntropyLoss(
         cobweb_rank_scores(q) / temperature, label) averaged over the batch ("mean", the
@@ -374,13 +430,31 @@ class CobwebWrapper:
         written back once with set_level_weights(w.tolist()).
         top_k: the cross-entropy over the exact top_k retrieved sentences plus the label instead
         of over all sentences (hard-negative training at retrieval speed; cwq_rank_ce_topk,
-        DESIGN §4.18).  Not together with level_weights: retrieval reads the baked weights."""
+        DESIGN §4.18).  Not together with level_weights: retrieval reads the baked weights.
+        allowed, or allowed_sets with set_of_query (no reference counterpart; what
+        cobweb_predict_batch accepts): the cross-entropy over the allowed sentences only -- a
+        tenant, ACL group or corpus split trains against its own negatives (cwq_rank_ce_masked /
+        cwq_rank_ce_topk_masked).  A label that is not allowed gives an infinite
+        loss for its query.  With top_k, allowed_sets is one call; without, each set runs once
+        over its queries.  Not together with level_weights (ValueError)."""
         if reduction not in ("mean", "sum", "none"):
             raise ValueError('reduction must be "mean", "sum" or "none"')
         if top_k is not None and level_weights is not None:
             raise ValueError("top_k and level_weights do not go together: retrieval reads the level weights baked "
                              "into the index (set_level_weights)")
         self.build_prediction_index()
+        if allowed is not None or allowed_sets is not None or set_of_query is not None:
+            q = torch.as_tensor(queries)
+            if q.dim() == 1:
+                q = q[None, :]
+            made, soq = self._loss_sets(allowed, allowed_sets, set_of_query, level_weights, q.shape[0])
+            try:
+                loss = self._masked_rank_ce(q, labels, temperature, top_k, made, soq)[0]
+            finally:
+                for m, mine in made:
+                    if mine:
+                        m.close()
+            return loss if reduction == "none" else loss.mean() if reduction == "mean" else loss.sum()
         if top_k is not None:
             from .autograd import rank_ce_topk_autograd
             loss = rank_ce_topk_autograd(self._index, torch.as_tensor(queries), labels, top_k, temperature)[0]
@@ -392,19 +466,36 @@ class CobwebWrapper:
             loss, _, _ = rank_ce_autograd(self._index, torch.as_tensor(queries), labels, temperature, level_weights)
         return loss if reduction == "none" else loss.mean() if reduction == "mean" else loss.sum()
 
-    def cobweb_target_ranks(self, queries, labels, level_weights=None, top_k=None):
+    def cobweb_target_ranks(self, queries, labels, level_weights=None, top_k=None, allowed=None, allowed_sets=None,
+                            set_of_query=None):
         """evaluate()'s two per-query numbers (src/training/cobweb_query_train.py:213-304)
         without forming a ranking: (rank [Q] int64, the 1-based position of the label in the
         Fast ranking -- -1 for a label outside the tree --, true_score [Q]).
         level_weights: the ranks under these level weights (recall / MRR of a schedule sweep
         against a fixed index).
         top_k: ranks from one top_k retrieval instead of a scan of all leaves, capped at
-        top_k + 1 ("at least top_k + 1"); not together with level_weights."""
+        top_k + 1 ("at least top_k + 1"); not together with level_weights.
+        allowed, or allowed_sets with set_of_query (as cobweb_ranking_loss takes them): the
+        label's rank among the allowed sentences only -- the rank the caller's own
+        cobweb_predict_batch(..., allowed=...) ranking gives it; -1 / -inf for a label that is
+        not allowed.  Not together with level_weights (ValueError)."""
         if top_k is not None and level_weights is not None:
             raise ValueError("top_k and level_weights do not go together: retrieval reads the level weights baked "
                              "into the index (set_level_weights)")
         self.build_prediction_index()
         with torch.no_grad():
+            if allowed is not None or allowed_sets is not None or set_of_query is not None:
+                q = torch.as_tensor(queries).detach()
+                if q.dim() == 1:
+                    q = q[None, :]
+                made, soq = self._loss_sets(allowed, allowed_sets, set_of_query, level_weights, q.shape[0])
+                try:
+                    _, tscore, rank = self._masked_rank_ce(q, labels, 1.0, top_k, made, soq)
+                finally:
+                    for m, mine in made:
+                        if mine:
+                            m.close()
+                return rank, tscore
             if top_k is not None:
                 _, _, tscore, rank, _, _ = self._index.rank_ce_topk(torch.as_tensor(queries).detach(), labels, top_k)
                 return rank, tscore

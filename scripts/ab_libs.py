@@ -14,7 +14,8 @@ by spaces when knobs contain commas: pass --libs once per arm).
     python scripts/ab_libs.py --libs a.so,b.so --rank-ce 1,16,256
 
 --rank-ce times cwq_rank_ce with its gradient instead (HIP events, the arms taking turns inside
-every repetition) and checks that the arms return the same bits.
+every repetition) and checks that the arms return the same bits; with --topk-loss K it times
+cwq_rank_ce_topk at that K the same way.
 
     python scripts/ab_libs.py --libs a.so,b.so --clusters 100 --categorize 1,64,1024
 
@@ -58,13 +59,18 @@ def env(kv):
                 os.environ[k] = v
 
 
-def rank_ce_ab(paths, arms, Q, nqs, reps):
+def rank_ce_ab(paths, arms, Q, nqs, reps, K=0):
     gen = torch.Generator(device=Q.device).manual_seed(7)
     T = float(arms[0].rank_scores(Q[:1]).std())
+    name = f"rank_ce_topk K={K}" if K else "rank_ce"
+
+    def run(ix, q, labels):
+        return ix.rank_ce_topk(q, labels, K, T, grad=True) if K else ix.rank_ce(q, labels, T, grad=True)
+
     for nq in nqs:
         q = Q[:nq].contiguous()
         labels = torch.randint(0, arms[0].n_sent, (nq,), device=Q.device, generator=gen)
-        outs = [ix.rank_ce(q, labels, T, grad=True) for ix in arms]
+        outs = [run(ix, q, labels) for ix in arms]
         same = all(torch.equal(a, b) for o in outs[1:] for a, b in zip(o, outs[0]))
         torch.cuda.synchronize()
         ts = [[] for _ in arms]
@@ -72,13 +78,13 @@ def rank_ce_ab(paths, arms, Q, nqs, reps):
             for i, ix in enumerate(arms):
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
-                ix.rank_ce(q, labels, T, grad=True)
+                run(ix, q, labels)
                 b.record()
                 b.synchronize()
                 ts[i].append(a.elapsed_time(b))
         med = [statistics.median(t) for t in ts]
         for p, t, m in zip(paths, ts, med):
-            print(f"rank_ce nq={nq} {os.path.basename(p)[:60]}: {m:.3f} ms [{min(t):.3f}, {max(t):.3f}]  "
+            print(f"{name} nq={nq} {os.path.basename(p)[:60]}: {m:.3f} ms [{min(t):.3f}, {max(t):.3f}]  "
                   f"x{m / med[0]:.4f} vs first, own spread {(max(t) - min(t)) / m:.1%}  "
                   f"{'same bits' if same else 'MISMATCH'}", flush=True)
 
@@ -147,6 +153,7 @@ def main():
     ap.add_argument("--share-index", action="store_true",
                     help="one index for every arm (same library; knobs read per call only)")
     ap.add_argument("--rank-ce", default="", help="query counts: time rank_ce (loss + grad_q) per arm instead")
+    ap.add_argument("--topk-loss", type=int, default=0, help="--rank-ce: time rank_ce_topk at this K instead")
     ap.add_argument("--categorize", default="", help="query counts: time categorize per arm instead")
     ap.add_argument("--masked", default="", help="query counts: time the single-mask score_topk(mask=) per arm instead")
     ap.add_argument("--fractions", default="1,0.5,0.1,0.01", help="--masked: allowed fractions")
@@ -186,7 +193,7 @@ def main():
     del fs
     torch.cuda.empty_cache()
     if args.rank_ce:
-        rank_ce_ab(paths, arms, Q, [int(v) for v in args.rank_ce.split(",")], args.reps)
+        rank_ce_ab(paths, arms, Q, [int(v) for v in args.rank_ce.split(",")], args.reps, args.topk_loss)
         return
     if args.masked:
         masked_ab(paths, arms, Q, [int(v) for v in args.masked.split(",")], [float(v) for v in args.fractions.split(",")],
