@@ -113,8 +113,12 @@ int cwq_index_info(const cwq_index* idx, int64_t* out8);
  * rows, out[3] = 1 when the per-call int8 panel was built, out[4] = the hub rows of the
  * batch filter's threshold sample (the rows with the largest query-independent key term,
  * appended to the strided sample; CWQ_FG_HUB_DIV = n at index creation: NL_iso / n rows,
- * 0: none). */
-int cwq_index_filter_info(const cwq_index* idx, int64_t* out5);
+ * 0: none), out[5] = the batch filter's launch schedule on this index by the default rules
+ * (0: bf16 launches only, 1: int8 from a quarter of the row tiles on, 2: the early schedule,
+ * bf16 sample pass and every launch on the int8 operands, 3: the direct schedule, int8
+ * sample pass with exact-key thresholds, every launch on the int8 operands), out[6] = 1 when the last
+ * Fast batch call ran the direct schedule. */
+int cwq_index_filter_info(const cwq_index* idx, int64_t* out7);
 
 /* The tree-adaptive cut the index chose (no reference counterpart): out[0] =
  * groups (centre nodes; 0: none planned), out[1] = top nodes (the root and the centres'

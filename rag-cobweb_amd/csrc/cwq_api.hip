@@ -1044,6 +1044,12 @@ extern "C" int cwq_index_info(const cwq_index* idx, int64_t* o) {
   return CWQ_OK;
 }
 
+// every row tile uniform (one parent: a flat tree's tiles), so one raw launch can cover them all
+static bool fg_flat_tiles(const cwq_index* ix) {
+  const size_t n = ix->tile_uni_prefix.size();
+  return n > 1 && (size_t)ix->tile_uni_prefix[n - 1] == n - 1 && !env_set("CWQ_FG_NO_ALLUNI");
+}
+
 extern "C" int cwq_index_filter_info(const cwq_index* idx, int64_t* o) {
   if (!idx || !o) return fail(CWQ_ERR_ARG, "NULL argument");
   o[0] = idx->grp_mode ? 1 : 0;
@@ -1051,6 +1057,11 @@ extern "C" int cwq_index_filter_info(const cwq_index* idx, int64_t* o) {
   o[2] = idx->n_grp_rows;
   o[3] = idx->i8_state > 0 ? 1 : 0;
   o[4] = idx->n_hub;
+  // the batch filter's schedule on this index by the default rules (fg_i8_from; the per-call
+  // knobs aside): 0 bf16 launches only, 1 the quarter rule, 2 the early schedule, 3 the direct one
+  const bool early = idx->i8_state > 0 && idx->i8_by_size && idx->n_hub > 0 && !idx->i8_early_off && !idx->grp_mode;
+  o[5] = idx->i8_state <= 0 ? 0 : !early ? 1 : (idx->iso_Sq && idx->iso_St && fg_flat_tiles(idx)) ? 3 : 2;
+  o[6] = idx->direct_ran ? 1 : 0;   // the last Fast batch call ran the direct schedule
   return CWQ_OK;
 }
 
@@ -1776,6 +1787,19 @@ bool build_i8(cwq_index* ix, hipStream_t s) {
           hipSuccess ||
       launch_tiles_i8(ix->iso_tf, ix->iso_rf8, (int)n_rt, ix->iso_tf8, s) != hipSuccess)
     return false;
+  // the direct schedule's sample panel: the sample rows of the int8 panel, gathered once (an
+  // index without hub rows never runs that schedule; without room for it the index keeps the
+  // bf16 sample pass)
+  if (ix->n_hub > 0 && ix->samp_rows && ix->ld_s > 0 && !ix->iso_Sq) {
+    int8_t* Sq = nullptr;
+    float4* St = nullptr;
+    if (!ix->alloc(&Sq, (size_t)ix->ld_s * ix->DPB) && !ix->alloc(&St, (size_t)ix->ld_s) &&
+        launch_gather_i8_rows(ix->iso_Mq, ix->DPB, ix->samp_rows, ix->ld_s, ix->iso_rf, ix->iso_rf8, Sq, St, s) ==
+            hipSuccess) {
+      ix->iso_Sq = Sq;
+      ix->iso_St = St;
+    }
+  }
   ix->i8_state = 1;
   return true;
 }
@@ -1799,11 +1823,19 @@ bool ensure_i8(cwq_index* ix, hipStream_t s) {
 // threshold: a call on the early schedule that ends above kFgCapQ / 4 candidates per query or
 // re-runs a query sends the index back to the quarter rule (note_i8_early; until
 // cwq_set_filter).  CWQ_FG_I8_EARLY (read per call; tests and A/Bs): 1: the early schedule on
-// an index of any size (building the panel), 0: the quarter rule.
+// an index of any size (building the panel), 2: the direct schedule (below) likewise, 0: the
+// quarter rule.
 // CWQ_FG_I8 (read per call; tests and in-process A/Bs):
 // negative: off; n >= 0: from phase n on, building the panel at any size.
 // A launch then takes them only when it is raw (all-uniform, Fast key).
-int fg_i8_from(cwq_index* ix, const int* cuts, int nph, bool cat, bool ib, hipStream_t s) {
+// The direct schedule (*direct): where the early schedule runs by the size rule --
+// or on an index of any size under CWQ_FG_I8_EARLY=2 -- on a flat index (every row tile
+// uniform) with its int8 sample panel, the sample pass ranks the sample rows on the int8
+// operands, the thresholds are exact keys of the rows it picks, and no bf16 query panel is
+// prepared (run_iso_filter).  CWQ_FG_I8_EARLY=1 keeps the early schedule as it was: bf16
+// sample pass with certified-bound thresholds.  The same guard covers both.
+int fg_i8_from(cwq_index* ix, const int* cuts, int nph, bool cat, bool ib, hipStream_t s, bool* direct) {
+  *direct = false;
   if (cat || ib || ix->grp_mode || ix->DPB % 64) return nph;
   const char* e = getenv("CWQ_FG_I8");
   if (e && *e) {
@@ -1813,6 +1845,7 @@ int fg_i8_from(cwq_index* ix, const int* cuts, int nph, bool cat, bool ib, hipSt
   const int ev = env_int("CWQ_FG_I8_EARLY", -1);
   if ((ev < 0 ? ix->i8_by_size : ev > 0) && ix->n_hub > 0 && !ix->i8_early_off && build_i8(ix, s)) {
     ix->i8_early_ran = true;
+    *direct = ev != 1 && ix->iso_Sq && ix->iso_St && fg_flat_tiles(ix);
     return 0;
   }
   if (ix->i8_state <= 0) return nph;
@@ -2196,9 +2229,19 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
   const int dir_cap = (int)std::min<int64_t>((int64_t)nqf * dir_per_q(ix), INT32_MAX / 2);
   int4* rec_dir = b.take<int4>((size_t)dir_cap);
   float2* pmm = (!cat && ix->n_multi_tiles) ? b.take<float2>((size_t)n_rt * nqf) : nullptr;
-  HIPCHK(launch_query_prep(qsrc, nqc, ix->D, ix->iso_c, ix->DPB, nqf, Xb, qinfo, s));
   const PathB pb = (!cat && ib) ? path_b(ix, c) : PathB{nullptr, 0, nullptr, nullptr};
   const bool grp = ix->grp_mode && c.Pg_lo;   // group-centred rows: the shifted prefix tables
+  // the launch schedule (fg_phase_cuts, fg_i8_from), chosen before the query prep: nothing on
+  // the direct schedule reads the bf16 query panel.  It keeps the phase cuts: one launch over
+  // every row tile (CWQ_FG_PHASES=0) passes as few candidates at C3 but its fgemm time measured
+  // 0.25 ms above the five launches' sum (DESIGN Appendix C.1)
+  int cuts[6] = {0, n_rt, n_rt, n_rt, n_rt, n_rt};
+  const int nph = fg_phase_cuts(n_rt, cuts);
+  bool direct = false;
+  const int i8_from = fg_i8_from(ix, cuts, nph, cat, ib, s, &direct);
+  direct = direct && !cat && !ib && !grp && !pb.dot && !pmm;
+  ix->direct_ran = direct;
+  if (!direct) HIPCHK(launch_query_prep(qsrc, nqc, ix->D, ix->iso_c, ix->DPB, nqf, Xb, qinfo, s));
   if (pmm)   // multi-parent tiles: parent-prefix range per (tile, query) for the pretest
     HIPCHK(launch_tile_prange(grp ? c.Pg_lo : c.P, grp ? c.Pg_hi : ib ? c.S_int : nullptr, c.ldP, c.pT, nqc, ix->iso_tf,
                               n_rt, pmm, nqf, s, &pb));
@@ -2240,10 +2283,26 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
   // large samples: lower bounds reduced to maxima over groups of 4 rows in the
   // kernel (fgemm_kernel<1>); small ones keep one value per row so that K groups exist
   g.lb = lb;
-  g.lbg = ix->n_samp >= 64 * K && !pb.dot ? 4 : 1;   // path-sum bounds: per-row values (fgemm_kernel<1>)
+  g.lbg = direct || (ix->n_samp >= 64 * K && !pb.dot) ? 4 : 1;   // path-sum bounds: per-row values (fgemm_kernel<1>)
   g.ldlb = ix->ld_s / g.lbg;
-  HIPCHK(launch_fgemm(Xb, ix->iso_Sb, g, ix->cus, s));
-  HIPCHK(launch_select(lb, g.ldlb, nqc, (int)g.ldlb, K, tl, tr, s));
+  bool i8_prepped = false;   // the int8 query side: once per chunk, before the first launch that reads it
+  if (direct) {
+    // approximate pass on the int8 operands (one ranking value and the row's place per group
+    // of 4 sample rows), the K best groups, T[q] = the K-th largest exact key of their rows
+    HIPCHK(launch_query_prep_i8(qsrc, nqc, ix->D, ix->iso_c, ix->DPB, nqf, Xq, qinfo8, s));
+    i8_prepped = true;
+    g.i8 = 1;
+    g.qinfo8 = qinfo8;
+    g.samp8 = ix->iso_St;
+    HIPCHK(launch_fgemm(Xq, ix->iso_Sq, g, ix->cus, s));
+    g.i8 = 0;
+    HIPCHK(launch_select(lb, g.ldlb, nqc, (int)g.ldlb, K, tl, tr, s, true));
+    HIPCHK(launch_sample_threshold(c.X, ix->iso_Mf, ix->DP, nqc, K, tl, tr, ix->samp_rows, ix->ld_s, ix->row_meta,
+                                   ix->row_par, c.P ? c.P : ix->dummy, c.pT ? 1 : c.ldP, tl + (K - 1), 64, s));
+  } else {
+    HIPCHK(launch_fgemm(Xb, ix->iso_Sb, g, ix->cus, s));
+    HIPCHK(launch_select(lb, g.ldlb, nqc, (int)g.ldlb, K, tl, tr, s));
+  }
   // group pruning: the sample saw only the groups kept; its seed threshold is a floor
   if (!cat && c.Tseed) HIPCHK(launch_raise_threshold(tl + (K - 1), 64, c.Tseed, nqc, s));
 
@@ -2263,11 +2322,7 @@ int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int 
   g.rec_dir = rec_dir;
   g.dir_cap = dir_cap;
   HIPCHK(hipMemsetAsync(qcnt, 0, ((size_t)5 * nqf + 64) * 4, s));
-  int cuts[6] = {0, n_rt, n_rt, n_rt, n_rt, n_rt};
-  const int nph = fg_phase_cuts(n_rt, cuts);
   ix->n_fg_launch = nph;
-  const int i8_from = fg_i8_from(ix, cuts, nph, cat, ib, s);
-  bool i8_prepped = false;   // the int8 query side: once per chunk, before the first launch that reads it
   g.qinfo8 = qinfo8;
   g.rf8 = ix->iso_rf8;
   g.tf8 = ix->iso_tf8;
@@ -2337,6 +2392,7 @@ int score_topk_impl(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_
   if (allow_filter) {
     ix->n_fg_i8 = 0;
     ix->i8_early_ran = false;
+    ix->direct_ran = false;
   }
   if (!general && allow_filter && use_filter(ix, k, kStreamMinRows) && use_stream(ix, nq, k))
     return stream_topk_impl(ix, q, nq, k, ids, scores, s);

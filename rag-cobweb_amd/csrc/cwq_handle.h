@@ -249,6 +249,11 @@ struct cwq_index {
   float root_w = 1.f, root_ld = 0.f;   // the root's level weight and logdet (host copies)
   int* samp_rows = nullptr;
   uint16_t* iso_Sb = nullptr;
+  // the direct schedule's sample operand (build_i8, on an index whose sample holds hub rows):
+  // the sample rows of iso_Mq in iso_Sb's row order, and their terms {pa, pb, s_r, -}
+  int8_t* iso_Sq = nullptr;
+  float4* iso_St = nullptr;
+  bool direct_ran = false;   // the current call ran the direct schedule (last_stats, filter_info)
   int64_t stats[6] = {0, 0, 0, 0, 0, 0};   // cwq_last_stats
   // timing (cwq_set_timing)
   bool timing = false;

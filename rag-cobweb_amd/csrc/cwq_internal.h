@@ -466,7 +466,9 @@ struct FgArgs {
   float root_w, root_ld;                  // mode 2: the root's level weight and logdet
   int64_t ldlb;
   int lbg;                                // sample: rows per lower-bound group (1 or 4)
-  int4* rec;                              // filter: appended records {q, row, u, l} (raw: {q, row, d, ex})
+  const float4* samp8;                    // sample on the int8 operands (mode 1 with i8): the sample rows' terms
+                                          // {pa, pb, s_r, -} (launch_gather_i8_rows), [nrows]
+  int4* rec;                             // filter: appended records {q, row, u, l} (raw: {q, row, d, ex})
   int64_t rec_cap;                        // record slots (a multiple of kFgChunk)
   int* gctr;                              // [0] chunks claimed, [1] direct records (zeroed before the launch)
   int4* rec_dir;                          // direct records (a tile with more than kFgCap)
@@ -647,6 +649,9 @@ __device__ __forceinline__ void select_values_wave(const float* __restrict__ uq,
 // >= 1024 floats of tail slack, masked here); g values per maximum, up to 16 while at
 // least 8*Kp maxima remain.  select_kernel (cwq_mfma.hip) and the per-call stream filter's
 // fused select (cwq_stream.hip) both run this, so their thresholds are identical.
+// ARG (the direct schedule's sample): a list entry's row is the position of the maximum
+// itself, not the last position of its run (distinct runs: still distinct positions).
+template <bool ARG = false>
 __device__ __forceinline__ void select_wave(const float* __restrict__ uq, int nrows, int Kp, int lane, float& lk,
                                             int& lr) {
   lk = -__builtin_inff();
@@ -659,21 +664,31 @@ __device__ __forceinline__ void select_wave(const float* __restrict__ uq, int nr
 #pragma unroll
     for (int t = 0; t < 4; ++t) v4[t] = *reinterpret_cast<const float4*>(uq + r0 + t * 256 + lane * 4);
     float m = -__builtin_inff();
+    int mi = 0;
+    (void)mi;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const float vv[4] = {v4[t].x, v4[t].y, v4[t].z, v4[t].w};
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int r = r0 + t * 256 + lane * 4 + c;
-        m = fmaxf(m, r < nrows ? vv[c] : -__builtin_inff());
+        if constexpr (ARG) {
+          if (r < nrows && vv[c] > m) {   // (a NaN never enters)
+            m = vv[c];
+            mi = r;
+          }
+        } else {
+          m = fmaxf(m, r < nrows ? vv[c] : -__builtin_inff());
+        }
         if (((t * 4 + c + 1) & (g - 1)) == 0) {
+          const int rr = ARG ? mi : r;
           if (r0 == 0 && t * 4 + c + 1 == g) {   // the empty list: sort the first maxima
             lk = m;
-            lr = m == -__builtin_inff() ? 0x7fffffff : r;
+            lr = m == -__builtin_inff() ? 0x7fffffff : rr;
             float dummy = 0.f;
             wave_sort64<false>(lk, lr, dummy, lane);
           } else {
-            list64_offer(lk, lr, lane, m, r, Kp);
+            list64_offer(lk, lr, lane, m, rr, Kp);
           }
           m = -__builtin_inff();
         }
@@ -832,7 +847,21 @@ hipError_t launch_query_prep(const float* q, int64_t nq, int D, const float* c, 
                              float4* qinfo, hipStream_t s, int* zero = nullptr, int nzero = 0);
 hipError_t launch_fgemm(const void* Xb, const void* Mb, const FgArgs& a, int n_wg, hipStream_t s);
 int fgemm_dpb(int D);   // padded bf16 operand width the fgemm build needs
-hipError_t launch_select(const float* u, int64_t ldu, int nq, int nrows, int Kp, float* cu, int* crow, hipStream_t s);
+// arg: crow gets the position of each list entry's own value in u (select_wave<true>), not the
+// last position of the run it was the maximum of
+hipError_t launch_select(const float* u, int64_t ldu, int nq, int nrows, int Kp, float* cu, int* crow, hipStream_t s,
+                         bool arg = false);
+// The direct schedule's sample: the sample rows of the int8 panel with their
+// row terms (built with the panel), the approximate pass over them (launch_fgemm, mode 1 with
+// i8 and samp8), launch_select(arg), then the exact keys of the K chosen rows:
+// T[q * ldT] = their K-th largest (-inf: fewer than K usable groups).  sel_v / sel_g: the
+// select's lists [nq][64]; a value's two low mantissa bits hold its row's place in the group.
+constexpr float kSampDead = -3.0e38f;   // approximate key of a padding / unusable sample row
+hipError_t launch_gather_i8_rows(const void* Mq, int DPB, const int* srow, int64_t n, const RowF* rf, const RowF* rf8,
+                                 void* Sq, float4* St, hipStream_t s);
+hipError_t launch_sample_threshold(const float* X, const float* Mf, int DP, int nq, int K, const float* sel_v,
+                                   const int* sel_g, const int* samp_rows, int n_samp_pad, const RowMeta* meta,
+                                   const int* par, const float* P, int64_t ldP, float* T, int64_t ldT, hipStream_t s);
 // Internal-node bound operands (hierarchical trees): for internal node i (ids [0, n)),
 // b' = [-w/2, mu'w] (w = A^2, A = 1/sqrtf(var), mu' = mean - c) as bf16 hi [ld][DPB2],
 // its RowF {R0 = M_n, beta, delta, rn2 = c_n, hs = wmax, hl = logdet, invL = level weight

@@ -135,6 +135,37 @@ hipError_t launch_gather_bf16_rows(const void* Mb, int DPB, const int* srow, int
   return hipGetLastError();
 }
 
+// The sample rows of the int8 panel as a compact operand, in iso_Sb's row order, with the row
+// terms of the approximate sample pass (fgemm_kernel<1, true, false, true>):
+// St[j] = {pa, pb, s_r, 0}, the approximate key of row j being pa + pb (s_x s_r acc) with
+// pa = fmaf(hs, rn2, hl), pb = -2 hs as in the bf16 sample pass.  Padding and unusable rows
+// get zeros and {kSampDead, 0, 0, 0}: a finite value below every key, so that the pass may
+// write a row's position into its value's low mantissa bits without forming a NaN.
+__global__ void gather_i8_rows_kernel(const int8_t* __restrict__ Mq, int DPB, const int* __restrict__ srow,
+                                      const RowF* __restrict__ rf, const RowF* __restrict__ rf8, int8_t* Sq,
+                                      float4* St) {
+  const int64_t j = blockIdx.x;
+  const int r = srow[j];
+  RowF f = RowF{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, -2};
+  if (r >= 0) f = rf[r];
+  const float pa = fmaf(f.hs, f.rn2, f.hl);
+  const bool ok = r >= 0 && f.par >= -1 && fabsf(pa) < -kSampDead;
+  typedef int v4i __attribute__((ext_vector_type(4)));
+  const v4i* src = reinterpret_cast<const v4i*>(Mq + (size_t)(ok ? r : 0) * DPB);
+  v4i* dst = reinterpret_cast<v4i*>(Sq + (size_t)j * DPB);
+  for (int i = threadIdx.x; i < DPB / 16; i += blockDim.x) dst[i] = ok ? src[i] : v4i{0, 0, 0, 0};
+  if (threadIdx.x == 0) St[j] = ok ? make_float4(pa, -2.f * f.hs, rf8[r].R0, 0.f) : make_float4(kSampDead, 0.f, 0.f, 0.f);
+}
+
+hipError_t launch_gather_i8_rows(const void* Mq, int DPB, const int* srow, int64_t n, const RowF* rf, const RowF* rf8,
+                                 void* Sq, float4* St, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (DPB % 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_i8_rows_kernel, dim3((unsigned)n), dim3(64), 0, s, (const int8_t*)Mq, DPB, srow, rf, rf8,
+                     (int8_t*)Sq, St);
+  return hipGetLastError();
+}
+
 // int8 split of one centred row or query (one wave; cwq_internal.h launch_rows_i8):
 // s = max|v| / 127, q = rint(v / s) clamped to +-127, hi = s q, lo = v - hi.  hi and lo are
 // formed in fp64, where both are exact (a 24-bit by 8-bit product; a difference within 31
@@ -844,13 +875,15 @@ __device__ __forceinline__ bool fg_raw_bounds(const FgArgs& a, int q, int row, f
 template <int MODE, bool ALLUNI, bool RAW = false, bool I8 = false>
 __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ Xb, const __bf16* __restrict__ Mb,
                                                     const FgArgs a) {
-  static_assert(!I8 || RAW, "int8 operands: raw-record launches only");
+  static_assert(!I8 || RAW || (MODE == 1 && ALLUNI), "int8 operands: raw-record launches and the approximate sample pass");
+  constexpr bool S8 = MODE == 1 && I8;   // the approximate sample pass (its epilogue's comment)
   typedef typename std::conditional<I8, i32x4, bf16x8>::type frag_t;
   typedef typename std::conditional<I8, i32x4, f32x4>::type acc_t;
   constexpr int ES = I8 ? 1 : 2;   // operand bytes per dim
   constexpr int SK = 64 / ES;      // dims per stage
   // (I8: + float2 [2][FT], the tile's row terms {R_r, s_r} by tile parity -- the epilogue reads
-  // them there, and no row term stays in registers over the K loop)
+  // them there, and no row term stays in registers over the K loop; S8: float4 [FT], the
+  // sample rows' {pa, pb, s_r, -})
   __shared__ __attribute__((aligned(16))) char smem[FLDS + (I8 ? 2 * FT * 8 : 0)];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1019,7 +1052,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     if (tid < FT) {
       qi = (I8 ? a.qinfo8 : a.qinfo)[qs];
       if (qs < a.nq && MODE == 0) Tq = a.T[(size_t)qs * a.ldT];
-      if (uni && tf.par >= 0 && qs < a.nq) {
+      if (!S8 && uni && tf.par >= 0 && qs < a.nq) {
         if (a.pb.dot) {
           pathb_bounds(a.pb, qs, tf.par, Pql, Pq);
         } else {
@@ -1028,7 +1061,15 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
         }
       }
       // I8: row r0 + tid's terms {R_r, s_r}, for LDS (s_r = 0 on unusable rows, whose R is -inf)
-      if (I8 && r0 + tid < a.nrows) rw8 = make_float2(a.rf[r0 + tid].R0, a.rf8[r0 + tid].R0);
+      if (I8 && !S8 && r0 + tid < a.nrows) rw8 = make_float2(a.rf[r0 + tid].R0, a.rf8[r0 + tid].R0);
+    }
+    if constexpr (S8) {
+      // the query scales s_x and the sample rows' terms: all the epilogue reads.  One buffer
+      // each: this instantiation ends every tile with a workgroup barrier (next_tile)
+      if (tid < FT) {
+        s_pi[tid] = qi.w;
+        reinterpret_cast<float4*>(smem + FLDS)[tid] = a.samp8[r0 + tid];
+      }
     }
     float R0[4], SR[4];
     (void)SR;
@@ -1042,7 +1083,7 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
     // RAW: the pretest terms alternate between two buffers by tile parity (the second one
     // in the s_qi region, which RAW tiles do not use)
     float* const s_qvt = RAW && (tile_no & 1) ? reinterpret_cast<float*>(smem + OFF_QI) : s_qv;
-    if (tid < FT) {
+    if (tid < FT && !S8) {
       const float T = Tq;
       // I8: the query scales s_x, by tile parity like the pretest terms, in the s_pi / s_pl
       // regions (RAW tiles do not use them)
@@ -1295,6 +1336,46 @@ __global__ __launch_bounds__(512) void fgemm_kernel(const __bf16* __restrict__ X
           }
         }
         __builtin_amdgcn_wave_barrier();   // reads of this block done before the next dump
+      }
+      goto flush;
+    }
+    if constexpr (S8) {
+      // Approximate sample pass on the int8 operands (the direct schedule).  Per
+      // element the approximate Fast key pa + pb (s_x s_r acc) of the bf16 pass, without its
+      // bounds: the value only RANKS the sample rows.  A group of 4 rows (r16 + 16 jb, all in
+      // this lane) keeps its maximum with the row's jb in the two low mantissa bits, and
+      // sample_threshold_kernel computes the exact fp32 keys of the rows select_kernel picks.
+      // Why the result cannot change: the K picked rows are distinct (distinct groups), and T
+      // is the K-th largest of their exact keys, so K distinct rows have key >= T and
+      // T <= tau_K, the K-th largest key of all rows.  Every true top-K row then has
+      // u >= key >= tau_K >= T (>= throughout) and passes the pretest -- conservative for
+      // u >= T -- and the bucket pass: the argument final_kernel's seeded T2 rests on.  The
+      // int8 ranking and the packed jb decide how tight T is, nothing else.
+      // No global load, no parent prefix (constant per query on a flat tree); padding rows
+      // hold kSampDead (finite, so packing forms no NaN); they and padding queries store -inf.
+      float4 rt4[4];
+#pragma unroll
+      for (int jb = 0; jb < 4; ++jb) rt4[jb] = reinterpret_cast<const float4*>(smem + FLDS)[wr * 64 + jb * 16 + r16];
+      const int g = (r0 + wr * 64) / 4 + r16;
+#pragma unroll
+      for (int ib = 0; ib < 8; ++ib) {
+        const int ql = wq * 128 + ib * 16 + 4 * c16;
+        const float4 sx4 = *reinterpret_cast<const float4*>(s_pi + ql);
+        const float sxj[4] = {sx4.x, sx4.y, sx4.z, sx4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float v[4];
+#pragma unroll
+          for (int jb = 0; jb < 4; ++jb) {
+            const float t = __fmul_rn(__fmul_rn((float)acc[ib][jb][j], rt4[jb].z), sxj[j]);
+            const float k = fmaf(rt4[jb].y, t, rt4[jb].x);
+            v[jb] = __int_as_float((__float_as_int(k) & ~3) | jb);
+          }
+          float m = __builtin_fmaxf(__builtin_fmaxf(v[0], v[1]), __builtin_fmaxf(v[2], v[3]));
+          const int q = q0 + ql + j;
+          if (!(m > 0.5f * kSampDead) || q >= a.nq) m = -CWQ_INF;   // (a NaN too)
+          a.lb[(size_t)q * a.ldlb + g] = m;
+        }
       }
       goto flush;
     }
@@ -1783,7 +1864,12 @@ hipError_t launch_fgemm(const void* Xb, const void* Mb, const FgArgs& a, int n_w
   if (a.DPB != fgemm_dpb(a.DPB) || a.n_qt <= 0 || a.n_rt <= 0) return hipErrorInvalidValue;
   if (a.qgroups * a.rgroups != 8) return hipErrorInvalidValue;
   n_wg = std::max(8, n_wg / 8 * 8);
-  if (a.mode == 1)
+  if (a.mode == 1 && a.i8) {   // the approximate sample pass; Xb / Mb: the int8 queries and sample rows
+    if (a.DPB % 64 || !a.qinfo8 || !a.samp8 || a.lbg != 4 || a.nrows != a.n_rt * kFgTile || !a.lb)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL((fgemm_kernel<1, true, false, true>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
+                       (const __bf16*)Mb, a);
+  } else if (a.mode == 1)
     hipLaunchKernelGGL((fgemm_kernel<1, false>), dim3((unsigned)n_wg), dim3(512), 0, s, (const __bf16*)Xb,
                        (const __bf16*)Mb, a);
   else if (a.mode == 2)
@@ -1884,6 +1970,7 @@ hipError_t launch_bucket(const int4* rec, const int* gctr, const int* chunk_fill
 // select: top-Kp values per query of a dense [nq][ld] array (the sample bounds; the
 // values are first reduced to maxima of up to 16 per lane)
 // ---------------------------------------------------------------------------
+template <bool ARG = false>
 __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ u, int64_t ldu, int nq, int nrows,
                                                      int Kp, float* cu, int* crow) {
   const int lane = threadIdx.x & 63;
@@ -1891,14 +1978,16 @@ __global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ u
   if (q >= nq) return;
   float lk;
   int lr;
-  select_wave(u + (size_t)q * ldu, nrows, Kp, lane, lk, lr);
+  select_wave<ARG>(u + (size_t)q * ldu, nrows, Kp, lane, lk, lr);
   cu[(size_t)q * 64 + lane] = lk;
   crow[(size_t)q * 64 + lane] = lr;
 }
 
-hipError_t launch_select(const float* u, int64_t ldu, int nq, int nrows, int Kp, float* cu, int* crow, hipStream_t s) {
-  hipLaunchKernelGGL(select_kernel, dim3((unsigned)((nq + kWavesPerWG - 1) / kWavesPerWG)), dim3(256), 0, s, u, ldu,
-                     nq, nrows, Kp, cu, crow);
+hipError_t launch_select(const float* u, int64_t ldu, int nq, int nrows, int Kp, float* cu, int* crow, hipStream_t s,
+                         bool arg) {
+  const dim3 grid((unsigned)((nq + kWavesPerWG - 1) / kWavesPerWG));
+  if (arg) hipLaunchKernelGGL(select_kernel<true>, grid, dim3(256), 0, s, u, ldu, nq, nrows, Kp, cu, crow);
+  else hipLaunchKernelGGL(select_kernel<false>, grid, dim3(256), 0, s, u, ldu, nq, nrows, Kp, cu, crow);
   return hipGetLastError();
 }
 
@@ -2167,6 +2256,63 @@ __device__ __forceinline__ float exact_iso_key(const float* __restrict__ X, cons
     slice(xg[(size_t)v * kXQ], m4);
   }
   return iso_key_tail(acc, md, pp, lp, cat, dconst);   // categorize: pp = BF[parent]
+}
+
+// The direct schedule's thresholds: one wave per query; lane j < K takes the
+// j-th group of select_kernel<true>'s list (sel_g: its position in the sample pass's group
+// array, sel_v: its value, whose two low mantissa bits hold the row's jb), resolves the
+// sample row and computes its key with exact_iso_key exactly as final_kernel's rounds call
+// it -- the same RowMeta, parent prefix and operation order, so bit for bit the key the
+// rerank and the exact scan produce.  T[q] = the K-th largest (the smallest) of the K keys:
+// K distinct rows have key >= T, so T <= the K-th largest key of all rows, and a row of
+// the true top-K, whose u >= key >= T, passes the filter (fgemm_kernel's sample epilogue
+// has the argument in full).  Which rows were picked decides only how tight T is.  -inf
+// when fewer than K groups are usable or a key is NaN (final_kernel then re-runs the query).
+// sel_v and T may share a buffer (T = sel_v + K - 1): every read precedes the one write.
+__global__ __launch_bounds__(256) void sample_threshold_kernel(const float* __restrict__ X, const float* __restrict__ Mf,
+                                                               int DP, int nq, int K, const float* sel_v,
+                                                               const int* __restrict__ sel_g,
+                                                               const int* __restrict__ samp_rows, int n_samp_pad,
+                                                               const RowMeta* __restrict__ meta,
+                                                               const int* __restrict__ par, const float* __restrict__ P,
+                                                               int64_t ldP, float* T, int64_t ldT) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * kWavesPerWG + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (q >= nq) return;
+  const bool act = lane < K;
+  float key = CWQ_INF;
+  bool bad = false;
+  if (act) {
+    const float v = sel_v[(size_t)q * 64 + lane];
+    const int gi = sel_g[(size_t)q * 64 + lane];
+    int rr = -1;
+    if (v > -CWQ_INF && (unsigned)gi < (unsigned)(n_samp_pad / 4)) {
+      // group gi = 16 (4 tile + wr) + r16 holds sample rows 64 (4 tile + wr) + 16 jb + r16
+      const int jb = __float_as_int(v) & 3;
+      rr = samp_rows[(gi >> 4) * 64 + jb * 16 + (gi & 15)];
+    }
+    if (rr >= 0) {
+      const int p = par[rr];
+      const RowMeta md = meta[rr];
+      const float pp = p < 0 ? 0.f : P[(size_t)q * ldP + p];
+      float lp = 0.f;
+      key = exact_iso_key(X, Mf, DP, q, rr, md, pp, lp);
+    }
+    bad = rr < 0 || !(key == key);
+  }
+  float m = act && !bad ? key : CWQ_INF;
+  for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
+  if (__ballot(bad) != 0) m = -CWQ_INF;
+  if (lane == 0) T[(size_t)q * ldT] = m;
+}
+
+hipError_t launch_sample_threshold(const float* X, const float* Mf, int DP, int nq, int K, const float* sel_v,
+                                   const int* sel_g, const int* samp_rows, int n_samp_pad, const RowMeta* meta,
+                                   const int* par, const float* P, int64_t ldP, float* T, int64_t ldT, hipStream_t s) {
+  if (K < 1 || K > 64 || n_samp_pad % kFgTile) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)((nq + kWavesPerWG - 1) / kWavesPerWG)), dim3(256), 0, s,
+                     X, Mf, DP, nq, K, sel_v, sel_g, samp_rows, n_samp_pad, meta, par, P, ldP, T, ldT);
+  return hipGetLastError();
 }
 
 // Raw sum S = sum_d (x_d A_d - B_d)^2 of internal node i for query q in the exact scan's

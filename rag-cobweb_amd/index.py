@@ -245,11 +245,14 @@ class CobwebIndex:
     def filter_info(self):
         """How the filters centre their rows (cwq_index_filter_info): group-centred rows on
         clustered trees, the number of groups / group-centred rows, the int8 panel, the hub
-        rows of the batch filter's threshold sample (of last_stats()["sample_rows"])."""
-        out = np.zeros(5, np.int64)
+        rows of the batch filter's threshold sample (of last_stats()["sample_rows"]), the batch
+        filter's launch schedule on this index by the default rules ("bf16", "quarter", "early"
+        or "direct") and whether the last Fast batch call ran the direct schedule."""
+        out = np.zeros(7, np.int64)
         check(self._L.cwq_index_filter_info(self._h, out.ctypes.data_as(ctypes.c_void_p)))
         return {"group_centred": bool(out[0]), "groups": int(out[1]), "group_rows": int(out[2]),
-                "int8_panel": bool(out[3]), "sample_hub_rows": int(out[4])}
+                "int8_panel": bool(out[3]), "sample_hub_rows": int(out[4]),
+                "schedule": ("bf16", "quarter", "early", "direct")[int(out[5])], "direct_last_call": bool(out[6])}
 
     def cut_info(self):
         """The tree-adaptive cut (cwq_index_cut_info): groups, top nodes (computed exactly by

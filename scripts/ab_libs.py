@@ -204,6 +204,8 @@ def main():
         return
     call = {p: [] for p in paths}
     fg = {p: [] for p in paths}
+    smp = {p: [] for p in paths}   # sample_ms (sample pass + select + thresholds) and rerank_ms per round
+    rer = {p: [] for p in paths}
     ref = None
     for r in range(args.rounds):
         for p, ix in zip(paths, arms):
@@ -215,7 +217,10 @@ def main():
                 call[p].append((time.perf_counter() - t0) * 1e3)
                 ix.set_timing(True)
                 ix.score_topk(Q, args.k)
-                fg[p].append(ix.last_timing()["fgemm_ms"])
+                tm = ix.last_timing()
+                fg[p].append(tm["fgemm_ms"])
+                smp[p].append(tm["sample_ms"])
+                rer[p].append(tm["rerank_ms"])
                 ix.set_timing(False)
                 if ref is None:
                     ref = (ids.cpu(), sc.cpu())
@@ -228,7 +233,8 @@ def main():
         mc, mf = statistics.median(call[p]), statistics.median(fg[p])
         st = ix.last_stats()   # of the arm's last call
         print(f"{os.path.basename(p)[:60]}: call {mc:.3f} ms ({args.queries / mc * 1e3:.0f} q/s)  fgemm {mf:.3f} ms "
-              f"(x{base / mf:.3f} vs first)  min {min(fg[p]):.3f}  cand/q {st['candidates']} reranks/q "
+              f"(x{base / mf:.3f} vs first)  min {min(fg[p]):.3f}  sample {statistics.median(smp[p]):.3f} ms  rerank "
+              f"{statistics.median(rer[p]):.3f} ms  cand/q {st['candidates']} reranks/q "
               f"{st['exact_reranks']} fallback {st['fallback_queries']} int8 launches {st.get('fg_i8_launches', 0)}",
               flush=True)
 

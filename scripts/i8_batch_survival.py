@@ -21,6 +21,9 @@ the rows, int8 after it; hybrid() below) -- profiles/fgi8_model_c3.log, DESIGN A
 the first int8 phase, launch by launch with the tighten passes (pipeline() below) --
 profiles/hub_model_c3.log.  With --full equal to --rows the model runs a shape as it is
 (the ratios the tests in tests/test_gpu_hub_sample.py ask for).
+--direct adds the table of the direct schedule (direct() below): the threshold from the exact
+keys of the rows an int8 ranking of the sample picks, against the certified-bound threshold,
+with five launches, one launch and a few other cuts -- profiles/direct_model_c3.log.
 """
 import argparse
 
@@ -42,7 +45,7 @@ def i8_split(v):
     return hi, v - hi
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=262_144)
     ap.add_argument("--queries", type=int, default=256)
@@ -51,7 +54,8 @@ def main():
     ap.add_argument("--full", type=int, default=1_000_000)
     ap.add_argument("--hybrid", action="store_true", help="also the bf16-then-int8 policy table (hybrid())")
     ap.add_argument("--hub", action="store_true", help="also the hub-sample / early int8 schedule table (hub())")
-    args = ap.parse_args()
+    ap.add_argument("--direct", action="store_true", help="also the direct-schedule table (direct())")
+    args = ap.parse_args(argv)
     rng = np.random.default_rng(0)
     N, Q, D = args.rows, args.queries, args.dim
     X = rng.standard_normal((N, D), dtype=np.float32)
@@ -95,6 +99,8 @@ def main():
         hybrid(args, S, dots, Xc, qs, gamma, K)
     if args.hub:
         hub(args, S, dots, Xc, qs, gamma, K)
+    if args.direct:
+        return direct(args, S, dots, Xc, qs, gamma, K)
 
 
 def sample_rows(N, norm2, sdiv=128, hub_div=None):
@@ -117,20 +123,25 @@ def sample_rows(N, norm2, sdiv=128, hub_div=None):
     return np.array(rows), len(hubs)
 
 
-def pipeline(S, wb, w8, wbt, w8t, K, samp, i8_from, cuts=(32, 96, 256, 512)):
+def pipeline(S, wb, w8, wbt, w8t, K, samp, i8_from, cuts=(32, 96, 256, 512), T0=None):
     """The batch filter's launches (run_iso_filter) in S units (smaller = better key): T = the
     K-th best certified bound of the bf16 sample pass (per 4-row group when the sample has
     >= 64 K rows), then one launch per row phase -- int8 bounds from phase i8_from on, bf16
     before -- each followed by the tighten pass (T = K-th best candidate bound so far).
     Returns per query: candidates, raw records (pretest with the 256-row tile maxima),
     reranks by the K-th-best-bound rule, reranks by the exact-seeded rule (final_kernel),
-    and the flagged shares of 16x64 blocks and 16x16 sub-blocks of the int8 launches."""
+    and the flagged shares of 16x64 blocks and 16x16 sub-blocks of the int8 launches.
+    T0: the thresholds the first launch runs with instead of the sample pass's bound (the
+    direct schedule's exact keys, exact_threshold()); cuts=(): one launch over every row."""
     Q, N = S.shape
-    sb = (S + wb)[:, samp]
-    if len(samp) >= 64 * K:
-        pad = (-len(samp)) % 4
-        sb = np.pad(sb, ((0, 0), (0, pad)), constant_values=np.inf).reshape(Q, -1, 4).min(2)
-    T = np.partition(sb, K - 1, axis=1)[:, K - 1]
+    if T0 is None:
+        sb = (S + wb)[:, samp]
+        if len(samp) >= 64 * K:
+            pad = (-len(samp)) % 4
+            sb = np.pad(sb, ((0, 0), (0, pad)), constant_values=np.inf).reshape(Q, -1, 4).min(2)
+        T = np.partition(sb, K - 1, axis=1)[:, K - 1]
+    else:
+        T = T0.copy()
     n_rt = (N + 255) // 256
     edges = [0]
     for f in cuts:
@@ -212,6 +223,67 @@ def hub(args, S, dots, Xc, qs, gamma, K):
         first = {3: "3 (a quarter)", 9: "none (bf16)"}.get(i8_from, str(i8_from))
         print(f"| {name} | {first} | {c.mean() * scale:.0f} | {raw.mean() * scale:.0f} | {100 * b64:.1f}% | "
               f"{100 * b16:.1f}% | {rer.mean() * scale:.0f} | {rer_s.mean() * scale:.0f} |", flush=True)
+
+
+def exact_threshold(S, S8, samp, K, pick=1):
+    """The direct schedule's threshold (sample_threshold_kernel) in S units: the sample rows are
+    ranked by the int8 dot's approximate key S8, one value per group of 4 sample rows; the
+    pick * K best groups' best rows are scored exactly and T is the K-th best of those exact
+    keys.  Valid whatever the ranking picks: K distinct rows have keys at least as good."""
+    Q = S.shape[0]
+    pad = (-len(samp)) % 4
+    a8 = np.pad(S8[:, samp], ((0, 0), (0, pad)), constant_values=np.inf).reshape(Q, -1, 4)
+    rows = np.pad(samp, (0, pad))[None, :].repeat(Q, 0).reshape(Q, -1, 4)
+    jb = a8.argmin(2)
+    grp = np.argpartition(a8.min(2), pick * K - 1, axis=1)[:, :pick * K]
+    chosen = np.take_along_axis(np.take_along_axis(rows, jb[:, :, None], 2)[:, :, 0], grp, 1)
+    return np.partition(np.take_along_axis(S, chosen, 1), K - 1, axis=1)[:, K - 1]
+
+
+def split_widths(Xc, qs, gamma, split, extra):
+    """Half-widths w of the certified bounds per (query, row) and wt, the pretest's, with the
+    256-row tile maxima of beta and delta (hub()'s and hybrid()'s widths), and the hi parts."""
+    N = Xc.shape[0]
+    rh, rl = split(Xc.astype(np.float64))
+    xh, xl = split(qs.astype(np.float64))
+    nh, nl = np.linalg.norm(rh, axis=1), np.linalg.norm(rl, axis=1)
+    beta = nl + (gamma * nh if extra is None else 0.0)
+    delta = nh + nl
+    a, c = np.linalg.norm(xh, axis=1)[:, None], np.linalg.norm(xl, axis=1)[:, None]
+    w = 2 * (a * beta[None, :] + c * delta[None, :]) + (0.0 if extra is None else 2 * extra)
+    nt = N // 256 * 256
+    bm = np.repeat(beta[:nt].reshape(-1, 256).max(1), 256)
+    dm = np.repeat(delta[:nt].reshape(-1, 256).max(1), 256)
+    wt = np.full_like(w, np.inf)   # (rows of a last partial tile: always flagged)
+    wt[:, :nt] = 2 * (a * bm[None, :] + c * dm[None, :])
+    return w, np.maximum(w, wt), xh, rh
+
+
+def direct(args, S, dots, Xc, qs, gamma, K):
+    """The direct schedule against the early one: hub S/2 sample, every launch on
+    the int8 operands, the first launch's threshold from the certified bf16 bounds of the sample
+    (today) or from exact keys of the rows the int8 ranking picks, by launch cuts.  Returns
+    {(threshold, cuts): candidates per query} for tests/test_direct_model_cpu.py."""
+    N = S.shape[1]
+    scale = args.full / N
+    wb, wbt, _, _ = split_widths(Xc, qs, gamma, lambda v: bf16_split(v.astype(np.float32)), None)
+    w8, w8t, xh8, rh8 = split_widths(Xc, qs, gamma, i8_split, 2.0 ** -21 * np.abs(dots))
+    norm2 = (Xc.astype(np.float64) ** 2).sum(1)
+    S8 = (qs.astype(np.float64) ** 2).sum(1)[:, None] + norm2[None, :] - 2 * (xh8 @ rh8.T)
+    samp, nh = sample_rows(N, norm2)
+    print(f"direct model, K = {K} of {N} x {Xc.shape[1]} rows, {S.shape[0]} queries, x{scale:.2f} to {args.full} "
+          f"rows; sample {len(samp)} rows ({nh} hub)")
+    print("| threshold | cuts | cand/q | raw records/q | 16x16 sub-blocks | reranks/q exact-seeded |")
+    out = {}
+    five = (32, 96, 256, 512)
+    for name, T0 in (("bf16 bound", None), ("exact keys", exact_threshold(S, S8, samp, K)),
+                     ("exact keys, 2K rows", exact_threshold(S, S8, samp, K, 2))):
+        for cuts in (five, ()) if T0 is None or "2K" in name else (five, (), (32,), (128,), (32, 256)):
+            c, raw, _, rer_s, _, b16 = pipeline(S, wb, w8, wbt, w8t, K, samp, 0, cuts, T0)
+            out[name, cuts] = c.mean() * scale
+            print(f"| {name} | {','.join(map(str, cuts)) or 'one launch'} | {c.mean() * scale:.0f} | "
+                  f"{raw.mean() * scale:.0f} | {100 * b16:.1f}% | {rer_s.mean() * scale:.0f} |", flush=True)
+    return out
 
 
 def hybrid(args, S, dots, Xc, qs, gamma, K):
