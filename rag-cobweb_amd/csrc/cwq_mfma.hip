@@ -2258,6 +2258,86 @@ __device__ __forceinline__ float exact_iso_key(const float* __restrict__ X, cons
   return iso_key_tail(acc, md, pp, lp, cat, dconst);   // categorize: pp = BF[parent]
 }
 
+// Wave-cooperative form of exact_iso_key's raw sum for up to 64 rows of one query (every
+// lane of the wave calls it; lane r < nrows passes row r's id in rr, -1: no row; nrows is
+// wave-uniform).  The per-lane form has each lane stream its own 3 KB row, so one load
+// instruction touches 64 cache lines; here the lanes take (row, 16-dim slice) items, 16
+// consecutive lanes the 16 consecutive slices of one row, so a load instruction reads four
+// contiguous 1 KB pieces.  The rows are walked kCoopCS slices at a time: an item computes
+// its partial exactly as exact_iso_key's slice() does (t * t, then the fma chain j = 1..15)
+// into the per-wave LDS array part[row][slice] (row stride kCoopLd: lane r's ordered reads
+// hit 64 banks), and lane r then adds row r's partials of the chunk in slice order
+// (acc += part) onto the sum it carries from the chunk before -- the additions of
+// exact_iso_key in its order, so the sum, and iso_key_tail of it, agree bit for bit.
+constexpr int kCoopCS = 16;               // slices per chunk (one query slice per lane and chunk)
+constexpr int kCoopLd = kCoopCS + 1;
+constexpr int kCoopPart = 64 * kCoopLd;   // floats of LDS per wave
+__device__ __forceinline__ float exact_iso_acc_coop(const float* __restrict__ X, const float* __restrict__ Mf, int DP,
+                                                    int q, int rr, int nrows, float* part) {
+  const int lane = threadIdx.x & 63;
+  const int NV16 = DP / 16;
+  const f32x16* __restrict__ xg = reinterpret_cast<const f32x16*>(X) + (size_t)(q / kXQ) * NV16 * kXQ + (q % kXQ);
+  const int s = lane & (kCoopCS - 1), rsub = lane / kCoopCS;
+  constexpr int RS = 64 / kCoopCS;   // rows per load instruction
+  constexpr int U = 4;               // load instructions in flight per lane
+  const bool mine = lane < nrows && rr >= 0;
+  float acc = 0.f;
+  for (int v0 = 0; v0 < NV16; v0 += kCoopCS) {
+    const int nv = min(kCoopCS, NV16 - v0);
+    const bool sv = s < nv;
+    f32x16 xa;
+    if (sv) xa = xg[(size_t)(v0 + s) * kXQ];
+    for (int r0 = 0; r0 < nrows; r0 += RS * U) {
+      float4 m4[U][4];
+      bool on[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int row = r0 + u * RS + rsub;
+        const int ru = __shfl(rr, row & 63, 64);
+        on[u] = sv && row < nrows && ru >= 0;
+        if (on[u]) {
+          const float* __restrict__ mr = Mf + (size_t)ru * DP + (size_t)(v0 + s) * 16;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) m4[u][j] = *reinterpret_cast<const float4*>(mr + j * 4);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (on[u]) {
+          float p;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const float4 t4 = m4[u][j >> 2];
+            const float mj = (j & 3) == 0 ? t4.x : (j & 3) == 1 ? t4.y : (j & 3) == 2 ? t4.z : t4.w;
+            const float t = xa[j] - mj;
+            p = (j == 0) ? t * t : fmaf(t, t, p);
+          }
+          part[(r0 + u * RS + rsub) * kCoopLd + s] = p;
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (mine) {
+      const float* pr = part + lane * kCoopLd;
+      if (nv == kCoopCS) {
+        float t[kCoopCS];
+#pragma unroll
+        for (int u = 0; u < kCoopCS; ++u) t[u] = pr[u];
+#pragma unroll
+        for (int u = 0; u < kCoopCS; ++u) acc += t[u];
+      } else {
+        for (int u = 0; u < nv; ++u) acc += pr[u];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  return acc;
+}
+
 // The direct schedule's thresholds: one wave per query; lane j < K takes the
 // j-th group of select_kernel<true>'s list (sel_g: its position in the sample pass's group
 // array, sel_v: its value, whose two low mantissa bits hold the row's jb), resolves the
@@ -2269,6 +2349,8 @@ __device__ __forceinline__ float exact_iso_key(const float* __restrict__ X, cons
 // has the argument in full).  Which rows were picked decides only how tight T is.  -inf
 // when fewer than K groups are usable or a key is NaN (final_kernel then re-runs the query).
 // sel_v and T may share a buffer (T = sel_v + K - 1): every read precedes the one write.
+// COOP: the K keys by exact_iso_acc_coop (a kernel of its own: neither form pays the other's registers)
+template <bool COOP>
 __global__ __launch_bounds__(256) void sample_threshold_kernel(const float* __restrict__ X, const float* __restrict__ Mf,
                                                                int DP, int nq, int K, const float* sel_v,
                                                                const int* __restrict__ sel_g,
@@ -2276,27 +2358,33 @@ __global__ __launch_bounds__(256) void sample_threshold_kernel(const float* __re
                                                                const RowMeta* __restrict__ meta,
                                                                const int* __restrict__ par, const float* __restrict__ P,
                                                                int64_t ldP, float* T, int64_t ldT) {
+  __shared__ float s_part[kWavesPerWG][kCoopPart];   // exact_iso_acc_coop's partials
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * kWavesPerWG + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (q >= nq) return;
   const bool act = lane < K;
   float key = CWQ_INF;
   bool bad = false;
+  int rr = -1;
   if (act) {
     const float v = sel_v[(size_t)q * 64 + lane];
     const int gi = sel_g[(size_t)q * 64 + lane];
-    int rr = -1;
     if (v > -CWQ_INF && (unsigned)gi < (unsigned)(n_samp_pad / 4)) {
       // group gi = 16 (4 tile + wr) + r16 holds sample rows 64 (4 tile + wr) + 16 jb + r16
       const int jb = __float_as_int(v) & 3;
       rr = samp_rows[(gi >> 4) * 64 + jb * 16 + (gi & 15)];
     }
+  }
+  // the K rows' raw sums by the whole wave (coop), or each lane its own row
+  float acc = 0.f;
+  if constexpr (COOP) acc = exact_iso_acc_coop(X, Mf, DP, q, rr, K, s_part[threadIdx.x >> 6]);
+  if (act) {
     if (rr >= 0) {
       const int p = par[rr];
       const RowMeta md = meta[rr];
       const float pp = p < 0 ? 0.f : P[(size_t)q * ldP + p];
       float lp = 0.f;
-      key = exact_iso_key(X, Mf, DP, q, rr, md, pp, lp);
+      key = COOP ? iso_key_tail(acc, md, pp, lp, 0, 0.f) : exact_iso_key(X, Mf, DP, q, rr, md, pp, lp);
     }
     bad = rr < 0 || !(key == key);
   }
@@ -2306,12 +2394,20 @@ __global__ __launch_bounds__(256) void sample_threshold_kernel(const float* __re
   if (lane == 0) T[(size_t)q * ldT] = m;
 }
 
+// CWQ_EXACT_COOP=0 (read per call: tests and in-process A/Bs switch it): the per-lane exact
+// keys in sample_threshold_kernel and final_kernel instead of the wave-cooperative ones
+static bool exact_coop_on() {
+  const char* e = getenv("CWQ_EXACT_COOP");
+  return !(e && *e && atoi(e) == 0);
+}
+
 hipError_t launch_sample_threshold(const float* X, const float* Mf, int DP, int nq, int K, const float* sel_v,
                                    const int* sel_g, const int* samp_rows, int n_samp_pad, const RowMeta* meta,
                                    const int* par, const float* P, int64_t ldP, float* T, int64_t ldT, hipStream_t s) {
   if (K < 1 || K > 64 || n_samp_pad % kFgTile) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)((nq + kWavesPerWG - 1) / kWavesPerWG)), dim3(256), 0, s,
-                     X, Mf, DP, nq, K, sel_v, sel_g, samp_rows, n_samp_pad, meta, par, P, ldP, T, ldT);
+  const auto kern = exact_coop_on() ? sample_threshold_kernel<true> : sample_threshold_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((nq + kWavesPerWG - 1) / kWavesPerWG)), dim3(256), 0, s, X, Mf, DP, nq, K,
+                     sel_v, sel_g, samp_rows, n_samp_pad, meta, par, P, ldP, T, ldT);
   return hipGetLastError();
 }
 
@@ -2422,6 +2518,8 @@ __device__ __forceinline__ float chain_prefix_cached(const float* __restrict__ X
 #endif
 constexpr bool kFinalSeeded = CWQ_FINAL_SEED != 0;
 
+// COOP (never with the chain): the rounds' keys by exact_iso_acc_coop, a kernel of its own
+template <bool COOP>
 __global__ __launch_bounds__(256) void final_kernel(const float* __restrict__ X, const float* __restrict__ Mf, int DP,
                                                     int nq, int K, int capq, const int* __restrict__ qcnt,
                                                     const int* __restrict__ qover, const int* __restrict__ crow,
@@ -2432,9 +2530,11 @@ __global__ __launch_bounds__(256) void final_kernel(const float* __restrict__ X,
                                                     float* pkey, float* paux, int* prow, int64_t lstride,
                                                     int* ok_flag, int* n_exact, const float* __restrict__ lkb,
                                                     const int* __restrict__ lrb, const int* __restrict__ done,
-                                                    const IntChain chain, int use_chain, int cat,
+                                                    const IntChain chain, int use_chain_arg, int cat,
                                                     float dconst) {
+  const int use_chain = COOP ? 0 : use_chain_arg;
   __shared__ int s_pend[kWavesPerWG][128];
+  __shared__ float s_part[kWavesPerWG][kCoopPart];   // exact_iso_acc_coop's partials
   __shared__ int s_ck[kWavesPerWG][kChainSlots];     // exact-prefix table (chain_prefix_cached)
   __shared__ float s_cv[kWavesPerWG][kChainSlots];
   const int lane = threadIdx.x & 63;
@@ -2503,11 +2603,22 @@ __global__ __launch_bounds__(256) void final_kernel(const float* __restrict__ X,
       const float pc = use_chain ? chain_prefix_cached(X, chain, DP, q, act && p > 0, p, P[(size_t)q * ldP],
                                                        s_ck[threadIdx.x >> 6], s_cv[threadIdx.x >> 6])
                                  : 0.f;
-      if (act) {
+      // the round's raw sums by the whole wave (coop: never with the chain), or each lane its row
+      if constexpr (COOP) {
+        const float acc = exact_iso_acc_coop(X, Mf, DP, q, act ? rr : -1, seed ? K : min(npend, 64),
+                                             s_part[threadIdx.x >> 6]);
+        if (act) {
+          const RowMeta md = meta[rr];
+          const float pp = p < 0 ? (cat ? CWQ_INF : 0.f) : P[(size_t)q * ldP + p];
+          key = iso_key_tail(acc, md, pp, lp, cat, dconst);
+        }
+      } else if (act) {
         const RowMeta md = meta[rr];
         // exact (cat: BF)
         float pp = p < 0 ? (cat ? CWQ_INF : 0.f) : (use_chain && p > 0 ? pc : P[(size_t)q * ldP + p]);
         key = exact_iso_key(X, Mf, DP, q, rr, md, pp, lp, cat, dconst);
+      }
+      if (act) {
         rid = seg_base + rr;
         ++nx;
       }
@@ -3183,9 +3294,10 @@ hipError_t launch_final(const float* X, const float* Mf, int DP, int nq, int K, 
     return hipGetLastError();
   }
   if (fx) return hipErrorInvalidValue;   // the fused tail exists in the workgroup-per-query form only
-  hipLaunchKernelGGL(final_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, X, Mf, DP, nq, K, capq, qcnt, qover,
-                     crow, cu, cl, T, ldT, meta, par, P, ldP, seg_base, pkey, paux, prow, lstride, ok_flag, n_exact,
-                     lkb, lrb, done, ch, chain ? 1 : 0, cat, dconst);
+  const auto kern = !chain && exact_coop_on() ? final_kernel<true> : final_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, X, Mf, DP, nq, K, capq, qcnt, qover, crow,
+                     cu, cl, T, ldT, meta, par, P, ldP, seg_base, pkey, paux, prow, lstride, ok_flag, n_exact, lkb, lrb,
+                     done, ch, chain ? 1 : 0, cat, dconst);
   return hipGetLastError();
 }
 
