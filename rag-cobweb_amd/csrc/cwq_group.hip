@@ -15,7 +15,7 @@
 // rounded outward into [P'lo, P'hi] (categorize: P'c = hs_c * sh with invL = 1, the
 // bottleneck min taken from BF separately).  The exact rerank keeps the exact P and the
 // uncentred fp32 rows, so results stay the exact scan's bit for bit.  The rounding of M
-// adds 2^-23 |M| to the rows' beta / delta (cwq_api.hip build_filter); its row-only cross
+// adds 2^-23 |M| to the rows' beta / delta (cwq_build.hip build_filter); its row-only cross
 // term 2^-23 |M| |M + d| stays within eps_n * rn2 for groups whose rows all have
 // |M| <= 2 |M + d| (plan_groups).
 #include <hip/hip_runtime.h>
@@ -77,7 +77,7 @@ hipError_t launch_group_norms(const float* mean, int D, const int64_t* nodes, in
   return hipGetLastError();
 }
 
-// The tree-adaptive cut (cwq_api.hip plan_groups): per isotropic row (one wave), |fl(mu_r -
+// The tree-adaptive cut (cwq_build.hip plan_groups): per isotropic row (one wave), |fl(mu_r -
 // c0)|^2 (out[r][0]) and |fl(mu_r - mu_a)|^2 for each internal ancestor a of the row at depth
 // 1..maxd (out[r][depth(a)]; -1: no ancestor at that depth), in fp64 -- the squared norms of
 // the row centred at the root or at a, as rows_prep would store it.  rpar: the row's parent

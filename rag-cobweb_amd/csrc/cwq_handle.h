@@ -1,8 +1,8 @@
 // The query library's host layer behind the C ABI: the handle (struct cwq_index), the per-call
 // scopes, the query chunk, and the declarations of the host functions that cross a file.
-// Host only: included by cwq_api.hip, cwq_rank.hip, cwq_fitcalls.hip, cwq_maskcalls.hip, cwq_sparsecalls.hip and
-// cwq_masklosscalls.hip and by nothing else; the
-// kernel sources share cwq_internal.h.
+// Host only: included by cwq_api.hip, cwq_build.hip, cwq_chunk.hip, cwq_filter.hip, cwq_topk.hip,
+// cwq_categorize.hip, cwq_rank.hip, cwq_fitcalls.hip, cwq_maskcalls.hip, cwq_sparsecalls.hip and
+// cwq_masklosscalls.hip and by nothing else; the kernel sources share cwq_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -462,9 +462,57 @@ struct Chunk {
   const RowMeta* meta = nullptr;   // [NL]
 };
 
+// Run-time knobs (environment variables, read where they are used: tests switch them in-process)
+inline int env_int(const char* name, int dflt) {   // the value of a non-empty setting, else dflt
+  const char* e = getenv(name);
+  return e && *e ? atoi(e) : dflt;
+}
+inline bool env_off(const char* name) {   // a non-empty setting that parses to 0
+  const char* e = getenv(name);
+  return e && *e && atoi(e) == 0;
+}
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+
+// Error-bound constants of the filter (cwq_mfma.hip header): fp32 accumulation of the
+// MFMA products (2x the textbook (n-1)u, n = DPB + 64), norm/centring rounding, and the
+// relative slack that covers the fp32 evaluation of both the bounds and the exact keys.
+struct FiltConsts {
+  double gamma, eps_n, slack;
+};
+inline FiltConsts filt_consts(int DPB) {
+  return {(DPB + 64) * std::ldexp(1.0, -23), std::ldexp(1.0, -20), std::ldexp(1.0, -16)};
+}
+
+constexpr int kFiltMinRows = 16384;   // automatic mode: below this the exact scan is as fast
+constexpr int kFiltMaxK = 64;         // the filter serves the list-based top-k path (k <= 64)
+constexpr int kFgRecPerQ = 512;       // candidate-record slots per query (append buffer)
+constexpr int kFgDirPerQ = 256;       // direct-record slots per query (tiles past kFgCap)
+// use_filter's min_rows on the per-call stream path (cwq_filter.hip)
+constexpr int kStreamMinRows = 512;
+// the most workgroups per query of the per-call path's rerank tail (fw_split, cwq_topk.hip)
+constexpr int kFwSplitMax = 32;
+
+// The buffers run_iso_filter (cwq_filter.hip) leaves for the caller's final pass.
+struct IsoFilter {
+  int *qcnt, *okf, *nex, *qover, *tdone, *crow, *tr;
+  float *cu, *cl, *tl, *tlk;
+};
+
 // ---- functions that cross a file, under the file that defines them ----
 
-// cwq_api.hip (the per-chunk exact passes, chunk sizing and carving)
+// cwq_api.hip
+bool fg_flat_tiles(const cwq_index* ix);
+
+// cwq_chunk.hip (the per-chunk exact passes, chunk sizing and carving)
+int group_tables(cwq_index* ix, Chunk& c, const float* q, bool cat, hipStream_t s);
+bool use_prune(const cwq_index* ix);
+int prune_internal(cwq_index* ix, Chunk& c, const float* q, int K, Bump& b, hipStream_t s, float* T0 = nullptr,
+                   int64_t ldT0 = 0, int* live = nullptr);
+int n_qblocks_for(int64_t nq, int kl);
+int pick_nslab(const cwq_index* ix, int nrows, int n_qblocks, int kl = 16);
+bool use_int_bounds(const cwq_index* ix);
+IntChain int_chain(const cwq_index* ix);
+bool small_scan_fits(const cwq_index* ix, int K);
 PathB path_b(const cwq_index* ix, const Chunk& c);
 int run_internal(cwq_index* ix, Chunk& c, hipStream_t s, bool bf_lpf = true, const float* q = nullptr,
                  int grp_cat = -1);
@@ -476,6 +524,24 @@ int run_leaf_scan(cwq_index* ix, const Chunk& c, int epi, bool cat, int kl, floa
 size_t chunk_bytes(const cwq_index* ix, int64_t nq_pad, bool full = true);
 void carve_chunk(cwq_index* ix, Bump& b, Chunk& c, int nq, bool full = true);
 int64_t chunk_queries(const cwq_index* ix, int64_t nq, size_t per_query_extra, bool full = true);
+
+// cwq_filter.hip (the batch filter shared by Fast and Basic, its policy and its int8 panel)
+bool use_filter(const cwq_index* ix, int k, int min_rows = kFiltMinRows, bool fast = true);
+void note_filter(cwq_index* ix);
+int fg_order();
+void fg_groups(int n_qt, int& qg, int& rg);
+bool i8_size_rule(const cwq_index* ix);
+bool ensure_i8(cwq_index* ix, hipStream_t s);
+void note_i8_early(cwq_index* ix, int64_t nq, int64_t cand_sum, int64_t n_fallback);
+size_t iso_filter_bytes_per_query(const cwq_index* ix, int n_rt);
+int run_iso_filter(cwq_index* ix, Chunk& c, const float* qsrc, int64_t nqf, int K, bool cat, bool ib, Bump& b,
+                   IsoFilter& o, hipStream_t s);
+
+// cwq_topk.hip (the per-call path's helpers that categorize shares; the host entry points' staging)
+hipError_t sync_spin(hipStream_t s);
+int stream_wgs(const cwq_index* ix);
+int fw_split(const cwq_index* ix, int nq, bool i8);
+int stage_host(cwq_index* ix, const float* q, size_t qbytes, size_t obytes, hipStream_t s);
 // (the unmasked Fast call for a caller that holds the handle: topk_reset, score_topk_impl + note_filter)
 void topk_begin(cwq_index* ix);
 int score_topk_unmasked(cwq_index* ix, const float* q, int64_t nq, int32_t k, int64_t* ids, float* scores,

@@ -1,5 +1,5 @@
 // Internal declarations shared by the libcwq kernels (cwq_kernels.hip) and the
-// C-ABI host runtime (cwq_api.hip and the host files behind cwq_handle.h).  Not part of the public interface.
+// C-ABI host runtime (the host files behind cwq_handle.h).  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -221,7 +221,7 @@ hipError_t launch_internal_finish(const IntFinishArgs& f, hipStream_t s);
 // B computes the groups with KUB >= T[q]; the groups left are certified to hold no top-K row.
 constexpr float kPruneSent = -1e24f;   // the pruned prefix (any real prefix is > kPruneCut)
 constexpr float kPruneCut = -1e20f;
-struct GroupBound {   // per group, fp64 (cwq_api.hip build_prune)
+struct GroupBound {   // per group, fp64 (cwq_build.hip build_prune)
   double r;           // >= max |mu_a - c_g| over the group's members (internal nodes and rows)
   double wmin, wmax;  // min / max per-dimension weight (A^2 or iv) over the members
   double ldmin, ldabs;   // min logdet, max |logdet| over the members
@@ -1213,7 +1213,7 @@ namespace cwq {
 // Allocate the device arrays of a tree of cap_nodes slots (f.D, f.pv set by the caller) into
 // f, every pointer recorded in allocs; false (nothing left allocated) when one fails.
 bool fit_alloc(FitDev& f, int cap_nodes, std::vector<void*>& allocs);
-// index_create_impl (cwq_api.hip) for inputs already on the device: mean and the compact
+// index_create_impl (cwq_build.hip) for inputs already on the device: mean and the compact
 // variances (VarSrc with its an_map); parent / node_of_sentence on the host
 int index_create_device(int device, int64_t n_nodes, int32_t dim, const float* mean, const VarSrc& var,
                         const int64_t* parent, const int64_t* node_of_sentence, int64_t n_sent,

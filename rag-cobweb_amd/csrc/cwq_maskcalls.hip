@@ -1,7 +1,7 @@
 // Masked Fast top-k (no reference counterpart): the cwq_mask handle,
 // cwq_score_topk_masked and cwq_score_topk_masked_multi.
 // Calls the launch_mask_* kernels (cwq_mask.hip), the exact per-chunk passes and the unmasked
-// Fast call of cwq_api.hip.
+// Fast call (cwq_chunk.hip, cwq_topk.hip).
 #include <atomic>
 #include <map>
 

@@ -1,7 +1,7 @@
 // Masked ranking loss (no reference counterpart): cwq_rank_ce_masked, the
 // cross-entropy loss, its gradient, the target's score and rank over a mask's allowed sentences,
 // and cwq_rank_ce_topk_masked, the truncated loss over the masked retrieval's top-K.
-// Calls the exact per-chunk passes (cwq_api.hip), the CE kernels (cwq_loss.hip), the key-writing
+// Calls the exact per-chunk passes (cwq_chunk.hip), the CE kernels (cwq_loss.hip), the key-writing
 // gathered scan (cwq_mask.hip), the backward's kernels (cwq_grad.hip) and, for the top-K form,
 // the masked Fast call (cwq_maskcalls.hip) and the pair kernels' host passes (cwq_sparsecalls.hip).
 #include "cwq_handle.h"

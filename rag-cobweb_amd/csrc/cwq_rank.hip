@@ -1,5 +1,5 @@
 // Scores over all leaves: call-time level weights, rank scores, their backward, the cross-entropy
-// loss, cwq_node_logprob and cwq_prefix_bounds.  Calls the chunk passes (cwq_api.hip).
+// loss, cwq_node_logprob and cwq_prefix_bounds.  Calls the chunk passes (cwq_chunk.hip).
 #include "cwq_handle.h"
 
 namespace {

@@ -104,7 +104,7 @@ def main(argv=None):
 
 
 def sample_rows(N, norm2, sdiv=128, hub_div=None):
-    """build_filter's threshold sample (cwq_api.hip): S = N/sdiv strided rows (whole 256-row
+    """build_filter's threshold sample (cwq_build.hip): S = N/sdiv strided rows (whole 256-row
     tiles), then H hub rows (lowest |mu'|^2 = largest row term on a flat tree; ties by row
     index; rows of the strided part skipped), H = S/2 or N/hub_div (0: none; none when
     N < 4 S), hub j in the 4-row group j mod H/4."""

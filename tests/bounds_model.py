@@ -76,7 +76,7 @@ def dpb(D):
 
 
 def filt_consts(D, operand):
-    """filt_consts (cwq_api.hip): gamma, eps_n, slack; the int8 dot is exact (gamma 0)."""
+    """filt_consts (cwq_handle.h): gamma, eps_n, slack; the int8 dot is exact (gamma 0)."""
     return ((dpb(D) + 64) * 2.0 ** -23 if operand == "bf16" else 0.0, 2.0 ** -20, 2.0 ** -16)
 
 
@@ -162,7 +162,7 @@ def model_bounds(x, rows, operand, scale=(1, 1, 1), weights=DEFAULT_W, consts=No
 
 
 def basic_consts(x, D):
-    """Basic's key on a flat tree's leaf (cwq_api.hip build_filter, cat): the full log-density
+    """Basic's key on a flat tree's leaf (cwq_build.hip build_filter, cat): the full log-density
     lp = -(logdet + D log 2 pi) / 2 - iv S / 2, no prefix term.  The filter takes it min'ed
     with the root's lp, so it orders only rows whose lp is below that."""
     x = np.atleast_2d(np.asarray(x, np.float64))
@@ -341,7 +341,7 @@ class Fixture:
 
 
 def sample_stride(N):
-    """The stride of the filter's threshold sample (cwq_api.hip build_filter): rows 0, stride, ..."""
+    """The stride of the filter's threshold sample (cwq_build.hip build_filter): rows 0, stride, ..."""
     return max(1, N // min(32768, max(FG_TILE, N // 128 // FG_TILE * FG_TILE)))
 
 

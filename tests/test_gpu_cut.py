@@ -1,4 +1,4 @@
-"""Tree-adaptive cut (cwq_api.hip plan_groups) on broad-rooted trees.
+"""Tree-adaptive cut (cwq_build.hip plan_groups) on broad-rooted trees.
 
 A Cobweb tree of a clustered corpus at scale has a few broad root children, each spanning
 many clusters (the 500k x 768 device-ifit tree: 37 root children over 500 clusters).  The

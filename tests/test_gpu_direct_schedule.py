@@ -1,4 +1,4 @@
-"""The batch filter's direct schedule (cwq_api.hip fg_i8_from / run_iso_filter, cwq_mfma.hip
+"""The batch filter's direct schedule (cwq_filter.hip fg_i8_from / run_iso_filter, cwq_mfma.hip
 fgemm_kernel<1, true, false, true> and sample_threshold_kernel): the sample pass ranks the
 sample rows on the int8 operands, T[q] is the K-th largest EXACT key of the K rows it picks,
 and no bf16 query panel is prepared.  CWQ_FG_I8_EARLY=2 (read per call) gives the small

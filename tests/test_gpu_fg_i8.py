@@ -1,6 +1,6 @@
 """Int8 first-level launches of the batch filter (fgemm_kernel<0, true, true, true> +
 bucket_raw_kernel's int8 bounds, cwq_mfma.hip; the policy and the CWQ_FG_I8 knob in
-cwq_api.hip run_iso_filter / fg_i8_from).  Every case compares the filter (cwq_set_filter 1)
+cwq_filter.hip run_iso_filter / fg_i8_from).  Every case compares the filter (cwq_set_filter 1)
 with the exact fp32 scan (mode 0): ids AND scores bit-identical.
 
 CWQ_FG_I8 is read per call: negative = bf16 only, n >= 0 = int8 from filter phase n on (the

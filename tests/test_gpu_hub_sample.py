@@ -1,5 +1,5 @@
-"""Hub rows in the batch filter's threshold sample and the early int8 schedule (cwq_api.hip
-build_filter / fg_i8_from / note_i8_early).  Every case compares the filter with the exact
+"""Hub rows in the batch filter's threshold sample and the early int8 schedule (cwq_build.hip
+build_filter; cwq_filter.hip fg_i8_from / note_i8_early).  Every case compares the filter with the exact
 fp32 scan (cwq_set_filter 0): ids AND scores bit-identical.
 
 The sample is the strided rows plus the rows with the largest query-independent key term
